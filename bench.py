@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: batch encode -> ids on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--sentences S] [--model uni32k|bpe32k|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--sentences S] [--model uni32k|bpe32k|...] [--full]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (classify -> normalize + segment + emit -> scan -> compact) over one batch of S
 synthetic sentences (default 10 M, ASCII, mean 128 B, length-bucketed; 32k unigram model) whose packed text and offsets
@@ -12,6 +13,11 @@ all ranks over RCCL, as BASELINE.json's north_star asks; the same run then times
 
 Prints ONE JSON line on rank 0.
   value         sentences/s of K unprofiled steps (barrier + synchronize on both sides, MAX over ranks)
+  ms_per_step   milliseconds of one of those steps
+
+A plain run sets up, warms up, times the K steps and prints the line (with N > 1 every gather form is timed: the headline
+is the faster of them).  --dump-outputs DIR writes what the last timed step returned on rank 0 (see dump_outputs).
+Everything below is measured only with --full:
   roofline      the dominant kernel (the streaming encode launch) over a second, PROFILED loop of the same steps: HIP
                 events around the launch on its stream; algorithmic bytes = L + 8 + 4 T' + 8 per sentence (SURVEY 8d);
                 `traffic` = HBM bytes per launch from the rocprofv3 PMC passes kept in profiles/pmc_traffic.json -- used
@@ -291,6 +297,32 @@ def model_blob(model):
         return f.read()
 
 
+DUMP_SENTENCES = 1 << 18      # sentences of the batch whose ids --dump-outputs writes (all of them in a smaller batch)
+DUMP_MAX_IDS = 12 << 20       # ... and at most this many ids (48 MB as float32)
+DUMP_SEED = 20250311
+
+
+def dump_outputs(path, d_ids, d_io, n, total):
+    """What a caller of the timed path receives -- ids (CSR in HBM), id offsets and the id count -- for a fixed, seeded
+    sample of the batch's sentences (the same sentences from run to run), as float arrays that hold the values exactly:
+      ids.npy         float32 [m]     the sampled sentences' ids, in sentence order
+      id_offsets.npy  float64 [k, 2]  where each sampled sentence's ids begin and end in the batch's id stream
+      id_count.npy    float64 [1]     the batch's number of ids
+    Sentences join the sample in a seeded order until DUMP_SENTENCES or DUMP_MAX_IDS is reached."""
+    import torch
+    io = d_io.cpu().numpy().astype(np.int64)
+    order = np.random.default_rng(DUMP_SEED).permutation(n)[:DUMP_SENTENCES]
+    counts = io[order + 1] - io[order]
+    pick = np.sort(order[:int(np.searchsorted(np.cumsum(counts), DUMP_MAX_IDS, side="right"))])
+    lens = io[pick + 1] - io[pick]
+    starts = np.repeat(io[pick] - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens) + np.arange(int(lens.sum()))
+    ids = d_ids[torch.from_numpy(starts).to(d_ids.device)].cpu().numpy() if len(starts) else np.zeros(0, np.int32)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ids.npy"), ids.astype(np.float32))
+    np.save(os.path.join(path, "id_offsets.npy"), np.stack([io[pick], io[pick + 1]], axis=1).astype(np.float64))
+    np.save(os.path.join(path, "id_count.npy"), np.array([total], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -309,6 +341,11 @@ def main():
                     help="how the ids travel: the library's all-gather (every rank padded to the largest capacity), or exact-size "
                          "point-to-point sends (world - 1 per rank, posted as one batch); default: time BOTH in this run "
                          "(sharding.IdGatherer algo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beside the headline: roofline (a second, profiled loop), the long-piece model, the "
+                         "side configurations, host-memory and Python forms, the CPU baseline (each --no-* below leaves one out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-second-model", action="store_true")
     ap.add_argument("--no-side-configs", action="store_true",
@@ -374,7 +411,7 @@ def main():
         args.sentences = len(offs) - 1
         args.no_second_model = args.no_side_configs = True
     second = None
-    if world == 1 and args.model == "uni32k" and not args.no_second_model and \
+    if args.full and world == 1 and args.model == "uni32k" and not args.no_second_model and \
             os.path.exists(os.path.join(ROOT, "tests", "golden", "uni32k_w16.model")):
         second = ("uni32k_w16",) + corpus_for("uni32k_w16", args.sentences, 20250227, args.unsorted)
     if not dry:
@@ -474,14 +511,17 @@ def main():
     # the headline is WITH the gather (the north star): the faster of the algorithms timed in this run
     head = min(with_ids, key=lambda m: results[m][0]) if with_ids else ("none" if "none" in results else "n/a")
     dt, total = results[head]
-    # a second, profiled loop for the per-kernel numbers (HIP events around every encode launch)
-    sp.SetProfiling(True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_ids, d_io, n, int(total))
     prof = []
-    for _ in range(args.steps):
-        encode_step()
-        prof.append(sp.LastProfile())
-    sync()
-    sp.SetProfiling(False)
+    if args.full:
+        # a second, profiled loop for the per-kernel numbers (HIP events around every encode launch)
+        sp.SetProfiling(True)
+        for _ in range(args.steps):
+            encode_step()
+            prof.append(sp.LastProfile())
+        sync()
+        sp.SetProfiling(False)
     if dist is not None:
         tot_t = torch.tensor([float(len(text)), float(total)], dtype=torch.float64, device=dev)
         dist.all_reduce(tot_t)
@@ -491,20 +531,6 @@ def main():
 
     if rank == 0:
         ms = dt / args.steps * 1e3
-        # dominant kernel = the launch that does the most of the batch's work (algorithmic bytes).  Since round 4 the general
-        # launch over the ~1 % of the sentences that are not plain ASCII runs NEXT TO the first word round on a second
-        # stream: it may last longer than the word round it hides behind (it is bound by the latency of its longest
-        # sentences), but it is not where the batch's bytes go; its own figures are in `roofline.beside`.
-        ncls = len(prof[0]["classes"])
-        k_ms = [sum(p["classes"][c]["kernel_ms"] for p in prof) / len(prof) for c in range(ncls)]
-        k_bytes = [prof[-1]["classes"][c]["bytes"] if prof[-1]["classes"][c]["kernel"] else 0 for c in range(ncls)]
-        dom = int(np.argmax(k_bytes))
-        longest = int(np.argmax(k_ms))
-        cls = prof[-1]["classes"][dom]
-        achieved = cls["bytes"] / (k_ms[dom] * 1e-3) / 1e9 if k_ms[dom] > 0 else 0.0
-        kname = cls["kernel"]
-        sha = kernel_sources_sha()
-        traffic, traffic_lower, traffic_note = traffic_on_record(args.model if args.corpus == "synthetic" else args.model + "@" + args.corpus, args.sentences, kname)
         out = {
             "metric": "sentences/sec EncodeBatch, %s %s, MI355X" % ("250k" if c5 else "32k",
                                                                      "unigram" if sp.model_type() == 1 else "bpe"),
@@ -530,48 +556,64 @@ def main():
                                                     (results["none"][0] if "none" in results else dt) / args.steps * 1e3),
                        "sharding": "dp%d by sentence" % world,
                        "handle": sp.HandleInfo(),      # device bytes of the model's tables, spmx_create's wall-clock ms
-                       "timed_loop": "profiling off; roofline.* comes from a second loop of the same steps with HIP events on"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
-                         "traffic_uncorrected": traffic_lower,
-                         "kernel_sources_sha": sha, "kernel": kname,
-                         "kernel_ms": k_ms[dom], "algorithmic_bytes_per_launch": cls["bytes"],
-                         "sentences_per_launch": cls["sentences"],
-                         "all_kernels_ms": {prof[-1]["classes"][c]["kernel"]: round(k_ms[c], 4)
-                                            for c in range(ncls) if prof[-1]["classes"][c]["kernel"]},
-                         "beside": None if longest == dom else {
-                             "kernel": prof[-1]["classes"][longest]["kernel"], "kernel_ms": k_ms[longest],
-                             "sentences_per_launch": prof[-1]["classes"][longest]["sentences"],
-                             "algorithmic_bytes_per_launch": prof[-1]["classes"][longest]["bytes"],
-                             "what": "the launch with the longest duration of the step: it runs on the second stream next to "
-                                     "the dominant kernel, over the sentences classify set aside"},
-                         "pipeline": {"algorithmic_bytes": sum(k_bytes), "ms": ms,
-                                      "achieved": sum(k_bytes) / (ms * 1e-3) / 1e9, "frac": sum(k_bytes) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                      "what": "every launch's algorithmic bytes over the whole step (classify, scan, compact included in the time)"},
-                         "phase_cycles": cls.get("phase_cycles"), "path": prof[-1]["path"],
-                         "pipeline_ms": sum(p["total_ms"] for p in prof) / len(prof)},
+                       "timed_loop": "profiling off" + ("; roofline.* comes from a second loop of the same steps with HIP events on"
+                                                       if args.full else "")},
         }
-        if world == 1 and out["roofline"]["beside"] is not None and not dry:
-            # the dominant kernel's duration when nothing shares the CUs with it: one profiled step on a second handle that
-            # runs the general launch BEFORE the word rounds (SPMX_NO_OVERLAP=1, read at load)
-            try:
-                os.environ["SPMX_NO_OVERLAP"] = "1"
-                sp1 = SentencePieceProcessor(model_proto=blob, device=local)
-                os.environ.pop("SPMX_NO_OVERLAP", None)
-                sp1.SetProfiling(True)
-                alone = []
-                for _ in range(3):
-                    sp1.EncodeDevice(d_text, d_offs, d_ids, d_io)
-                    alone.append([c["kernel_ms"] for c in sp1.LastProfile()["classes"] if c["kernel"] == kname][0])
-                sync()
-                a_ms = sorted(alone)[1]
-                out["roofline"]["alone"] = {"kernel_ms": a_ms, "achieved": cls["bytes"] / (a_ms * 1e-3) / 1e9,
-                                            "frac": cls["bytes"] / (a_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                            "what": "the same kernel with the general launch run before it instead of beside it"}
-                del sp1
-            except Exception as e:
-                os.environ.pop("SPMX_NO_OVERLAP", None)
-                out["roofline"]["alone"] = {"failed": repr(e)[:200]}
+        if args.full:
+            # dominant kernel = the launch that does the most of the batch's work (algorithmic bytes).  Since round 4 the general
+            # launch over the ~1 % of the sentences that are not plain ASCII runs NEXT TO the first word round on a second
+            # stream: it may last longer than the word round it hides behind (it is bound by the latency of its longest
+            # sentences), but it is not where the batch's bytes go; its own figures are in `roofline.beside`.
+            ncls = len(prof[0]["classes"])
+            k_ms = [sum(p["classes"][c]["kernel_ms"] for p in prof) / len(prof) for c in range(ncls)]
+            k_bytes = [prof[-1]["classes"][c]["bytes"] if prof[-1]["classes"][c]["kernel"] else 0 for c in range(ncls)]
+            dom = int(np.argmax(k_bytes))
+            longest = int(np.argmax(k_ms))
+            cls = prof[-1]["classes"][dom]
+            achieved = cls["bytes"] / (k_ms[dom] * 1e-3) / 1e9 if k_ms[dom] > 0 else 0.0
+            kname = cls["kernel"]
+            sha = kernel_sources_sha()
+            traffic, traffic_lower, traffic_note = traffic_on_record(args.model if args.corpus == "synthetic" else args.model + "@" + args.corpus, args.sentences, kname)
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
+                               "traffic_uncorrected": traffic_lower,
+                               "kernel_sources_sha": sha, "kernel": kname,
+                               "kernel_ms": k_ms[dom], "algorithmic_bytes_per_launch": cls["bytes"],
+                               "sentences_per_launch": cls["sentences"],
+                               "all_kernels_ms": {prof[-1]["classes"][c]["kernel"]: round(k_ms[c], 4)
+                                                  for c in range(ncls) if prof[-1]["classes"][c]["kernel"]},
+                               "beside": None if longest == dom else {
+                                   "kernel": prof[-1]["classes"][longest]["kernel"], "kernel_ms": k_ms[longest],
+                                   "sentences_per_launch": prof[-1]["classes"][longest]["sentences"],
+                                   "algorithmic_bytes_per_launch": prof[-1]["classes"][longest]["bytes"],
+                                   "what": "the launch with the longest duration of the step: it runs on the second stream next to "
+                                           "the dominant kernel, over the sentences classify set aside"},
+                               "pipeline": {"algorithmic_bytes": sum(k_bytes), "ms": ms,
+                                            "achieved": sum(k_bytes) / (ms * 1e-3) / 1e9, "frac": sum(k_bytes) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                            "what": "every launch's algorithmic bytes over the whole step (classify, scan, compact included in the time)"},
+                               "phase_cycles": cls.get("phase_cycles"), "path": prof[-1]["path"],
+                               "pipeline_ms": sum(p["total_ms"] for p in prof) / len(prof)}
+            if world == 1 and out["roofline"]["beside"] is not None and not dry:
+                # the dominant kernel's duration when nothing shares the CUs with it: one profiled step on a second handle that
+                # runs the general launch BEFORE the word rounds (SPMX_NO_OVERLAP=1, read at load)
+                try:
+                    os.environ["SPMX_NO_OVERLAP"] = "1"
+                    sp1 = SentencePieceProcessor(model_proto=blob, device=local)
+                    os.environ.pop("SPMX_NO_OVERLAP", None)
+                    sp1.SetProfiling(True)
+                    alone = []
+                    for _ in range(3):
+                        sp1.EncodeDevice(d_text, d_offs, d_ids, d_io)
+                        alone.append([c["kernel_ms"] for c in sp1.LastProfile()["classes"] if c["kernel"] == kname][0])
+                    sync()
+                    a_ms = sorted(alone)[1]
+                    out["roofline"]["alone"] = {"kernel_ms": a_ms, "achieved": cls["bytes"] / (a_ms * 1e-3) / 1e9,
+                                                "frac": cls["bytes"] / (a_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                                "what": "the same kernel with the general launch run before it instead of beside it"}
+                    del sp1
+                except Exception as e:
+                    os.environ.pop("SPMX_NO_OVERLAP", None)
+                    out["roofline"]["alone"] = {"failed": repr(e)[:200]}
         if multi:
             for mode, (mdt, _) in results.items():
                 key = mode.replace("ids:", "")
@@ -620,7 +662,7 @@ def main():
                 out["long_piece_model"]["probe_ids_bit_exact"] = None
                 out["long_piece_model"]["probe_error"] = repr(e)[:200]
             del sp2, dt2_text, dt2_offs, i2, io2
-        if world == 1 and args.model == "uni32k" and not args.no_side_configs:
+        if args.full and world == 1 and args.model == "uni32k" and not args.no_side_configs:
             # the other single-GPU configurations of BASELINE.json, compact: c3 (the same corpus through the 32k BPE
             # model), c5 (250k-piece unigram, mixed script, 1 M sentences), documents (8192 x 16 KB, 256 x 1 MiB)
             try:
@@ -673,7 +715,7 @@ def main():
                     del td, od
             except Exception as e:
                 out["docs"] = {"failed": repr(e)[:300]}
-        if world == 1 and not args.no_side_configs:
+        if args.full and world == 1 and not args.no_side_configs:
             # host arrays in, host arrays out (SURVEY 8d's end-to-end figure): pack is the caller's, the call copies the text
             # to the GPU in chunks, encodes, copies the ids back -- the chunk pipeline of spmx_encode_batch (PCIe-inclusive;
             # never `value`)
@@ -746,7 +788,7 @@ def main():
                 del strs, got, raw
             except Exception as e:
                 out["end_to_end_python"] = {"failed": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             io_h = d_io.cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(text, offs, blob, np.diff(io_h), d_ids[:int(io_h[-1])].cpu().numpy(), io_h)
     else:

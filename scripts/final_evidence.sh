@@ -1,6 +1,6 @@
 # usage (GPU box): bash scripts/final_evidence.sh <tag>  -- the round's evidence on the head's sources, most important first:
 # smoke, PMC traffic passes (every record of the bench line) merged into profiles/pmc_traffic.json, rocprofv3 kernel stats
-# (uni32k, c5_250k), SQ counters, then the default bench line (which picks the fresh traffic records up).  SKIP_TESTS=1
+# (uni32k, c5_250k), SQ counters, then the --full bench line (which picks the fresh traffic records up).  SKIP_TESTS=1
 # leaves the full GPU suite out (run it separately: python -m pytest tests -m gpu).  QUICK=1: headline + C5 only.
 TAG=${1:-r06}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
@@ -46,5 +46,5 @@ GROUPS_MAX=2 bash scripts/pmc_sq.sh 2000000 > $O/uni32k_2m_pmc_sq.txt 2>&1; rm -
 MODEL=c5_250k GROUPS_MAX=2 bash scripts/pmc_sq.sh 1000000 > $O/c5_1m_pmc_sq.txt 2>&1; rm -rf gpurun_out/pmc_sq
 fi
 cp profiles/pmc_traffic.json $O/pmc_traffic_used.json
-( time timeout 1500 python bench.py > $O/bench_uni32k_10m.json 2> $O/bench.err ) 2> $O/bench_wall.txt; tail -3 $O/bench_wall.txt; tail -c 600 $O/bench_uni32k_10m.json
+( time timeout 1500 python bench.py --full > $O/bench_uni32k_10m.json 2> $O/bench.err ) 2> $O/bench_wall.txt; tail -3 $O/bench_wall.txt; tail -c 600 $O/bench_uni32k_10m.json
 ls $O

@@ -20,7 +20,12 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        subprocess.check_call(["make", "-s", "-C", EMU_DIR])
+        # several processes may get here at once in a fresh tree (the ranks of tests/test_bench_multirank.py): one make at a
+        # time, or one of them links objects another is still writing
+        import fcntl
+        with open(os.path.join(EMU_DIR, "Makefile"), "rb") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            subprocess.check_call(["make", "-s", "-C", EMU_DIR])
         from sentencepiece_amd import _capi
         _lib = _capi.bind(EMU_SO)
     return _lib

@@ -19,14 +19,14 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _run(world, extra_env, timeout, torchrun=True, gpus=None):
+def _run(world, extra_env, timeout, torchrun=True, gpus=None, extra_args=()):
     env = dict(os.environ)
     env.update(extra_env)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):          # (the launch decides them)
         env.pop(k, None)
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     args = [os.path.join(ROOT, "tests", "bench_dryrun.py"), "--gpus", str(world if gpus is None else gpus), "--steps", "1",
-            "--warmup", "1", "--sentences", "4500", "--model", "uni32k"]
+            "--warmup", "1", "--sentences", "4500", "--model", "uni32k"] + list(extra_args)
     if torchrun:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port())] + args
@@ -38,7 +38,7 @@ def _run(world, extra_env, timeout, torchrun=True, gpus=None):
 
 
 def test_bench_two_ranks_times_both_gathers_and_prints_one_line():
-    p, lines = _run(2, {}, 600)
+    p, lines = _run(2, {}, 600, extra_args=["--full"])      # (--full: the roofline's profiled loop too)
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, p.stdout[-2000:]
     d = json.loads(lines[0])
@@ -110,3 +110,45 @@ def test_bench_one_rank_runs_the_multi_rank_control_flow():
     for k in ("value_gather_all_gather", "value_gather_p2p_exact", "value_gather_none"):
         assert d[k] > 0, k
     assert d["config"]["gather"].startswith("ids:")
+
+
+def test_bench_plain_line_and_dumped_outputs():
+    """A plain one-GPU run (no --full): the headline and nothing measured beside it, and --dump-outputs writes the last
+    timed step's ids of a fixed sample of the batch -- the same files from run to run, the oracle's ids."""
+    import tempfile
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from tests import oraclelib
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SPMX_BENCH_ONE_RANK_GATHER"):
+        env.pop(k, None)
+    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+    with tempfile.TemporaryDirectory() as td:
+        dumps = []
+        for run in ("a", "b"):
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_dryrun.py"), "--gpus", "1", "--steps", "3",
+                                "--warmup", "1", "--sentences", "3000", "--model", "uni32k", "--dump-outputs", os.path.join(td, run)],
+                               cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+            lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+            assert p.returncode == 0 and len(lines) == 1, (p.stdout[-1000:], p.stderr[-2000:])
+            d = json.loads(lines[0])
+            assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "sentences/s" and d["higher_is_better"]
+            assert d["ms_per_step"] > 0 and abs(d["value"] - 3000 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+            for k in ("roofline", "long_piece_model", "c3", "c5", "end_to_end", "end_to_end_python", "cpu_baseline"):
+                assert k not in d, k
+            files = sorted(os.listdir(os.path.join(td, run)))
+            assert files == ["id_count.npy", "id_offsets.npy", "ids.npy"], files
+            dumps.append({f[:-4]: np.load(os.path.join(td, run, f)) for f in files})
+        a, b = dumps
+        for k in a:
+            assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+        text, offs = bench.corpus_for("uni32k", 3000, 20250227, False)
+        oids, oio = oraclelib.OracleLib().load(bench.model_blob("uni32k")).encode_batch(text, offs)
+        oio = np.asarray(oio).astype(np.int64)
+        assert a["id_count"][0] == oio[-1]
+        # (a batch smaller than the sample: every sentence, in order)
+        assert np.array_equal(a["id_offsets"], np.stack([oio[:-1], oio[1:]], axis=1).astype(np.float64))
+        assert np.array_equal(a["ids"], np.asarray(oids)[:oio[-1]].astype(np.float32))

@@ -1,9 +1,10 @@
 """include/spmx_reference_binding.h -- the subclass INTEGRATION.md section 2 shows -- compiled against the reference's
 own header and objects (oracle/_ref/obj, made by oracle/Makefile from the sources where they lie) and the product's C
 ABI, then driven through a ``sentencepiece::SentencePieceProcessor*`` with spm_encode's loop next to the unmodified
-base class (tests/cpp/ref_binding_test.cc).  The CPU run links the emulated library; the GPU run uses the binary that
-``__graft_entry__.build()`` / this module made in the build container against libspmx.so (the GPU box has no
-/root/reference to compile against)."""
+base class (tests/cpp/ref_binding_test.cc).  The CPU run links the emulated library, the GPU run libspmx.so.  Compiling
+the driver needs the reference's header: ``__graft_entry__.build()`` compiles it where the reference tree is and joins it
+with the reference's objects into one relocatable object under oracle/_ref/, which is all the link needs wherever the
+test runs."""
 import glob
 import os
 import subprocess
@@ -15,12 +16,26 @@ from tests import fixtures
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 BIN = os.path.join(ROOT, "tests", "cpp", "ref_binding_test")
+OBJ = os.path.join(ROOT, "oracle", "_ref", "ref_binding_test.o")     # the driver and the reference's objects, linked with -r
 
 
 def build(emu):
-    """-> path of the binary, or None where the reference tree / its objects are not there."""
-    objs = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "obj", "**", "*.o"), recursive=True))
-    if not os.path.isdir(os.path.join(REF, "src")) or not objs:
+    """-> path of the binary, or None where neither the reference tree and its compiled objects nor OBJ are there."""
+    if os.path.isdir(os.path.join(REF, "src")):
+        objs = sorted(glob.glob(os.path.join(ROOT, "oracle", "_ref", "obj", "**", "*.o"), recursive=True))
+        if not objs:
+            return None
+        deps = [os.path.join(ROOT, "tests", "cpp", "ref_binding_test.cc"), os.path.join(ROOT, "include", "spmx_reference_binding.h"),
+                os.path.join(ROOT, "include", "spmx.h")] + objs
+        if not os.path.exists(OBJ) or os.path.getmtime(OBJ) < max(os.path.getmtime(p) for p in deps):
+            inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle", "_ref"), "-I" + REF, "-I" + REF + "/src",
+                   "-I" + REF + "/src/builtin_pb", "-I" + REF + "/third_party", "-I" + REF + "/third_party/protobuf-lite"]
+            drv = OBJ + ".driver.o"
+            subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-pthread", "-DHAVE_PTHREAD=1", "-D_USE_INTERNAL_STRING_VIEW"] + inc +
+                                  ["-c", "-o", drv, deps[0]])
+            subprocess.check_call(["g++", "-r", "-nostdlib", "-o", OBJ, drv] + objs)
+            os.remove(drv)
+    if not os.path.exists(OBJ):
         return None
     out = BIN + ("_emu" if emu else "")
     lib = os.path.join(ROOT, "tests", "emu") if emu else os.path.join(ROOT, "sentencepiece_amd")
@@ -30,13 +45,9 @@ def build(emu):
     so = os.path.join(lib, "libspmx_emu.so" if emu else "libspmx.so")
     if not os.path.exists(so):
         return None
-    srcs = [os.path.join(ROOT, "tests", "cpp", "ref_binding_test.cc"), os.path.join(ROOT, "include", "spmx_reference_binding.h"),
-            os.path.join(ROOT, "include", "spmx.h"), so]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in srcs):
-        inc = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "oracle", "_ref"), "-I" + REF, "-I" + REF + "/src",
-               "-I" + REF + "/src/builtin_pb", "-I" + REF + "/third_party", "-I" + REF + "/third_party/protobuf-lite"]
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-w", "-pthread", "-DHAVE_PTHREAD=1", "-D_USE_INTERNAL_STRING_VIEW"] + inc +
-                              ["-o", out, srcs[0]] + objs + ["-L" + lib, "-lspmx_emu" if emu else "-lspmx", "-Wl,-rpath," + lib, "-lpthread"])
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in (OBJ, so)):
+        subprocess.check_call(["g++", "-pthread", "-o", out, OBJ, "-L" + lib, "-lspmx_emu" if emu else "-lspmx", "-Wl,-rpath," + lib,
+                               "-lpthread"])
     return out
 
 
@@ -62,9 +73,9 @@ def test_reference_binding_emulated(model, opts, tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("model,opts", CASES)
 def test_reference_binding_gpu(model, opts):
-    b = build(emu=False) or (BIN if os.path.exists(BIN) else None)
+    b = build(emu=False)
     if b is None:
-        pytest.skip("tests/cpp/ref_binding_test was not prebuilt (no reference tree in the build container)")
+        pytest.skip("no compiled reference objects here (oracle/_ref is made by __graft_entry__.build() where the reference is)")
     args = [b, os.path.join(fixtures.GOLDEN, model + ".model"), os.path.join(fixtures.GOLDEN, "botchan.txt")] + ([opts] if opts else [])
     out = subprocess.run(args, capture_output=True, text=True)
     assert out.returncode == 0, out.stderr
