@@ -785,6 +785,22 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
   if ((h->dev.flags & kNfCompressSp) && (h->dev.flags & kNfByteFallback)) expand = 2;   // slots: bytes + 2 per space symbol
   // (a slot per sentence: its normalized length + the extra ids, rounded to groups of 4 with 3 ids of slack for alignment)
   uint64_t arena_need = expand * text_bytes + (10 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * n + 4096;
+  // (the word rounds' second round takes fresh slots: with a sentence-per-lane first round -- not direct -- and most of a
+  // batch deferred, the two rounds together can outgrow this bound; the batch is then encoded again once, with the arena
+  // arena_head asked for, and the workspace keeps that arena for its next calls)
+  // DIRECT: both word rounds in the word-per-lane form over a model whose words normalize by themselves -- the first
+  // round takes the sentences in input order, 64 to a tile, and finds a sentence's length class itself where it matters
+  // (kernels.h EncodeArgs::direct): no classify pass, no read-back of its counts
+  const bool direct = word_ok && any_word && h->word_form == 3 && !h->no_direct && streaming;
+  // ... its tiles' id regions sit at the arena's start, one id unit per byte + 1 + n_extra per sentence
+  // (kernels_wordwave.h): int32 entries, arena_head starts behind them
+  const bool ids16 = h->model.pieces.size() <= 65536 && !h->no_ids16;
+  uint64_t direct_region = 0;
+  if (direct) {
+    const uint64_t units = text_bytes + (1 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * n;
+    direct_region = ((ids16 ? (units + 1) / 2 : units) + 7) & ~static_cast<uint64_t>(3);
+    arena_need += direct_region;
+  }
   const bool prof = h->profiling;
   if (prof) HIP_OR_RETURN(h, EnsureEvents(ws));
   const uint32_t n32 = static_cast<uint32_t>(n);
@@ -811,6 +827,9 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     // (blocks of documents go to a second launch, by the whole chip; a batch of ten million short sentences has none and
     // does not pay for that launch)
     const uint32_t big = (n < 65536 || text_bytes > 160ull * n) ? h->compact_big : 0u;
+    // (a call may compact twice -- behind the exact-capacity and long launches: the list of document blocks starts empty
+    // every time, or the second compaction appends past the end of d_big_list)
+    if (big) HIP_OR_RETURN(h, hipMemsetAsync(&ws->d_ctrl->big_count[0], 0, sizeof(uint32_t), stream));
     CompactArgs pa{ws->d_arena.p, ws->d_tmp_off.p, ws->d_counts.p, d_id_offsets, d_ids, d_ids ? ids_capacity : 0, n32, &ws->d_ctrl->status, h->compact_staged,
                    big, ws->d_big_list.p, &ws->d_ctrl->big_count[0]};
     const uint64_t cblocks = (n + 63) / 64;
@@ -827,7 +846,8 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
   if (h->arena_first && arena_need > h->arena_first) { arena_need = h->arena_first; arena_cap_limit = h->arena_first; }
   // (the pipelined host form's largest chunk: Workspace::reserve_text_bytes -- capacity only, the call's own need decides the rest)
   const uint64_t arena_reserve = (h->arena_first || ws->reserve_text_bytes <= text_bytes) ? 0 :
-      expand * ws->reserve_text_bytes + (10 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * (ws->reserve_n > n ? ws->reserve_n : n) + 4096;
+      expand * ws->reserve_text_bytes + (10 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * (ws->reserve_n > n ? ws->reserve_n : n) + 4096 +
+      (direct ? (ws->reserve_text_bytes + (1 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * (ws->reserve_n > n ? ws->reserve_n : n)) / (ids16 ? 2 : 1) + 8 : 0);
   for (int attempt = 0; attempt < 4; ++attempt) {
     HIP_OR_RETURN(h, ws->d_arena.Reserve(arena_need > arena_reserve ? arena_need : arena_reserve));
     if (spans) HIP_OR_RETURN(h, ws->d_arena_tb.Reserve(ws->d_arena.cap));
@@ -835,10 +855,6 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     HIP_OR_RETURN(h, hipMemsetAsync(ws->d_ctrl, 0, sizeof(Ctrl), stream));
     HIP_OR_RETURN(h, hipMemsetAsync(d_status, 0, n, stream));
     for (bool &u : ws->slot_used) u = false;
-    // DIRECT: both word rounds in the word-per-lane form over a model whose words normalize by themselves -- the first
-    // round takes the sentences in input order, 64 to a tile, and finds a sentence's length class itself where it matters
-    // (kernels.h EncodeArgs::direct): no classify pass, no read-back of its counts
-    const bool direct = word_ok && any_word && h->word_form == 3 && !h->no_direct && streaming;
     uint32_t known[kMaxClasses] = {0};       // the class lists: every sentence, or (scanned) the plain ones
     uint32_t gen_known[kMaxClasses] = {0};   // (scanned) the sentences set aside for the general kernels
     uint64_t gen_total = 0;
@@ -1217,7 +1233,8 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
         wa.dyn_mask = h->dyn_slots - 1u;
         wa.dyn_cap = h->dyn_list_cap;
         wa.resume = ws->d_resume.p;
-        wa.ids16 = (h->model.pieces.size() <= 65536 && !h->no_ids16) ? 1u : 0u;
+        wa.ids16 = ids16 ? 1u : 0u;
+        wa.arena_first = (direct && mode != 2) ? direct_region : 0u;   // (the first round's tile regions)
         snprintf(ws->slot_name[slot], sizeof(ws->slot_name[slot]), "%s",
                  wform ? (wa.ids16 ? (mode == 2 ? "EncodeWordWaveAgainKernel<true>" : mode == 1 ? "EncodeWordWaveCollectKernel<true>" : "EncodeWordWaveKernel<true>")
                                    : (mode == 2 ? "EncodeWordWaveAgainKernel<false>" : mode == 1 ? "EncodeWordWaveCollectKernel<false>" : "EncodeWordWaveKernel<false>"))
@@ -1382,6 +1399,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       }
       p.path[0] = ws->h_ctrl->side.n_backlog; p.path[1] = ws->h_ctrl->side.over_count; p.path[2] = ws->h_ctrl->side.long_count;
       p.path[3] = ws->h_ctrl->side.n_failed;
+      p.path[4] = static_cast<uint64_t>(attempt);   // (encodes of the batch again with a larger arena)
       HIP_OR_RETURN(h, hipEventElapsedTime(&p.total_ms, ws->ev[kNumSlots][0], ws->ev[kNumSlots][1]));
       std::lock_guard<std::mutex> l(h->mu);
       h->prof = p;
@@ -1398,6 +1416,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       HIP_OR_RETURN(h, ws->d_tok_begin.Reserve(total));
       CompactArgs pa{ws->d_arena_tb.p, ws->d_tmp_off.p, ws->d_counts.p, d_id_offsets, ws->d_tok_begin.p, total, n32, nullptr, h->compact_staged,
                      h->compact_big, ws->d_big_list.p, &ws->d_ctrl->big_count[1]};
+      if (h->compact_big) HIP_OR_RETURN(h, hipMemsetAsync(&ws->d_ctrl->big_count[1], 0, sizeof(uint32_t), stream));
       const uint64_t cblocks = (n + 63) / 64;
       const uint64_t cgrid = cblocks < static_cast<uint64_t>(h->n_cu) * 32 ? cblocks : static_cast<uint64_t>(h->n_cu) * 32;
       HIP_OR_RETURN(h, LaunchCompact(pa, static_cast<int>(cgrid), stream));
@@ -3214,7 +3233,7 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
     // L + 8 + 4 T' + 8 per sentence
     if (bytes) bytes[c] = p.raw_bytes[c] + 16 * p.sentences[c] + 4 * p.ids[c];
   }
-  if (path) for (int k = 0; k < 4; ++k) path[k] = p.path[k];
+  if (path) for (int k = 0; k < 5; ++k) path[k] = p.path[k];
   if (total_ms) *total_ms = p.total_ms;
   return p.n;
 }

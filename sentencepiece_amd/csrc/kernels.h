@@ -121,6 +121,9 @@ struct EncodeArgs {
   // null: sentence first + lane) or of one list (row 0 of lists); a sentence's length class -- which only says whether it
   // is a document (cls[].general) and which list it goes to when the word form hands it on -- is found from cls[].rcap
   uint32_t direct;
+  // (direct, first round) int32 entries at the arena's start that hold the first round's tile regions (sentence s of the
+  // batch from id unit offs[s] - offs[0] + s * (1 + n_prefix + n_suffix)); arena_head is moved past them once per launch
+  uint64_t arena_first;
   // ---- sentence-per-wave launch (BPE models that are not word-wise; kernels_bpe.h) ----
   const uint32_t *list;         // sentence indices of this length class
   const uint32_t *list_count;   // number of entries in list (device resident)

@@ -569,8 +569,9 @@ SPMX_DEVICE void encode_word_block_as(const EncodeArgs &a, unsigned char *smem) 
     const int len = mine ? static_cast<int>(l64) : 0;
     // ---- a slot of cap ids in the arena (at most one id per byte of the normalized form: the bytes + 1) ----
     const int cap = mine ? len + 1 : 0;
-    // (second round: the sentence keeps the slot -- and the ids -- the first round gave it)
-    const int room = (mine && MODE != kWmDyn) ? (cap + n_extra + 3 + 3) & ~3 : 0;
+    // (second round: a slot of its own too -- the word-per-lane first round packs its sentences' ids back to back, so
+    // nothing may be appended behind them in place; the ids in front of the resume point are copied over below)
+    const int room = mine ? (cap + n_extra + 3 + 3) & ~3 : 0;
     int total = 0;
     const int excl = wave_excl_scan(room, lane, &total);
     unsigned long long base = 0;
@@ -585,9 +586,19 @@ SPMX_DEVICE void encode_word_block_as(const EncodeArgs &a, unsigned char *smem) 
     int32_t *slot = a.arena + base + static_cast<unsigned long long>(excl + shift) + d.n_prefix;
     WordResume rs{0, 0, 0.f};
     if (MODE == kWmDyn && mine) {
-      slot = a.arena + a.tmp_off[sid] + d.n_prefix;
       const U4 r = a.resume[sid];
       rs.p = static_cast<int>(r.x); rs.n = static_cast<int>(r.y); rs.B = wv::bits_to_float(r.z);
+      // where the first round left them: tmp_off in id units (kTmpOffHalf: 16-bit ids), the sentence's extra ids in front
+      const uint64_t t = a.tmp_off[sid];
+      const uint64_t src = ((t & kTmpOffHalf) ? (t & ~kTmpOffHalf) : (H16 ? 2ull * t : t)) + static_cast<uint64_t>(d.n_prefix);
+      if (!overflow && rs.n > 0 && rs.n <= cap) {
+        if (H16) {
+          const uint16_t *f16 = reinterpret_cast<const uint16_t *>(a.arena) + src;
+          for (int x = 0; x < rs.n; ++x) reinterpret_cast<uint16_t *>(slot)[x] = f16[x];
+        } else {
+          for (int x = 0; x < rs.n; ++x) slot[x] = a.arena[src + x];
+        }
+      }
     }
     int steps = 0;
     int n = uni_word_lane<DP, MODE, H16>(a, a.text, beg, len, slot, cap, T, mine && !overflow, &steps, &rs);
@@ -618,7 +629,8 @@ SPMX_DEVICE void encode_word_block_as(const EncodeArgs &a, unsigned char *smem) 
       const bool gone = left && !again;
       if (again) {                                   // where the second round takes the sentence up again
         a.resume[sid] = U4{static_cast<uint32_t>(rs.p), static_cast<uint32_t>(rs.n), wv::float_to_bits(rs.B), 0u};
-        a.tmp_off[sid] = static_cast<unsigned long long>(slot - d.n_prefix - a.arena);
+        a.tmp_off[sid] = H16 ? kTmpOffHalf | (2ull * static_cast<unsigned long long>(slot - a.arena) - static_cast<unsigned long long>(d.n_prefix))
+                             : static_cast<unsigned long long>(slot - d.n_prefix - a.arena);
       }
       append_lanes(wv::ballot(again), again, sid, a.left_lists + static_cast<uint64_t>(c) * a.n, &a.left_counts[c], lane);
       append_lanes(wv::ballot(gone), gone, sid, a.left2_lists + static_cast<uint64_t>(c) * a.n, &a.left2_counts[c], lane);

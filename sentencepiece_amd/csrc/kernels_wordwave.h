@@ -28,14 +28,17 @@
 //           add scan over the packed pair, one max scan that hands every lane its sentence's first lane's value, a scalar
 //           carry for the sentence that continues from the previous 64 words) -- exact integers, compared with the entry's
 //           limit; so is the unknown-piece run across words (the neighbour lane's flag);
-//   ids     consecutive words are consecutive ids: a word's ids go straight to its sentence's slot at the offset the scan
-//           gave it (neighbouring lanes write neighbouring addresses).
+//   ids     consecutive words are consecutive ids, and so are the tile's sentences: a word's ids go to the tile's arena
+//           region at the place the same scan's UNSEGMENTED sum gives it (a scalar carry across batches), every sentence
+//           behind the one before it with its extra ids -- a dense stream that neighbouring lanes write and the compaction
+//           reads by whole lines.
 //
 // A sentence either gets the reference's ids or nothing (status bits per sentence in LDS: "again" = every word it lacks is
-// in the call-local memo now, "gone" = not for the word form); the lists, the resume record, the arena slots, tmp_off and
-// counts are exactly what encode_word_block_as leaves, so resolve, the other round, the tail launch, scan and compact do
-// not care which of the two forms ran a round.  (The second round in this form starts its sentences over: a lane's work
-// is a word, not the rest of a sentence.)
+// in the call-local memo now, "gone" = not for the word form); the lists, the resume record, tmp_off (id units, kTmpOffHalf
+// for 16-bit ids) and counts are what encode_word_block_as leaves, so resolve, the other round, the tail launch, scan and
+// compact do not care which of the two forms ran a round.  A sentence given up leaves dead ids in the stream: nothing reads
+// them.  The second round takes a region of its own (the next sentence's ids follow the first round's) and copies the ids
+// in front of its resume point there.
 #ifndef SPMX_KERNELS_WORDWAVE_H_
 #define SPMX_KERNELS_WORDWAVE_H_
 
@@ -123,6 +126,10 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
   const bool any_word = (d.flags & kNfWordLocalNorm) != 0;
   const uint64_t tbase = reinterpret_cast<uint64_t>(a.text);
   WaveCounters tc;
+  // (direct first round) what comes after this launch -- the second round, the tail -- takes its slots behind the tile
+  // regions, which follow from the input offsets (below); nothing else asks arena_head while this launch runs
+  if (MODE != kWmDyn && a.arena_first != 0u && wv::block_id() == 0 && wv::wave_in_block() == 0 && lane == 0)
+    wv::atomic_add(a.arena_head, static_cast<unsigned long long>(a.arena_first));
   WwStage SA{}, SB{};                                               // the two batches of the word pipeline (below)
   uint32_t dyn_warm = 0u;                                           // (collecting round) batches for which stage A still asks the call-local memo's tags
   for (;;) {
@@ -149,32 +156,58 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
     }
     // (a class marked `general` passes through: documents belong to the wave-cooperative form, kernels_uniwave.h)
     const bool mine = have && !a.cls[cl].general && l64 <= kWwMaxLen;
-    // ---- a slot of cap ids in the arena per sentence, as encode_word_block_as lays them out ----
-    const int cap = mine ? static_cast<int>(l64) + 1 : 0;
-    // (round 6 tried half-size slots for 16-bit ids -- lines twice as full for the compaction: no change in the step, 5.43 ms
-    // against 5.38: CompactKernel is bound by its 1.1 GB of 32-bit output, not by the sparse reads)
-    const int room = (mine && MODE != kWmDyn) ? (cap + n_extra + 3 + 3) & ~3 : 0;
-    int total = 0;
-    const int excl = wave_excl_scan(room, lane, &total);
-    unsigned long long base = 0;
-    if (lane == 0 && total > 0) base = wv::atomic_add(a.arena_head, static_cast<unsigned long long>(total + 3));
-    base = (static_cast<unsigned long long>(wv::shfl(static_cast<uint32_t>(base >> 32), 0)) << 32) |
-           wv::shfl(static_cast<uint32_t>(base), 0);
-    const bool overflow = base + static_cast<unsigned long long>(total + 3) > a.arena_cap;
-    if (overflow && lane == 0) wv::atomic_or(a.status, kStArenaOverflow);
-    base = (base + 3ull) & ~3ull;
-    const int at = excl + d.n_prefix;
-    const int shift = (4 - (at & 3)) & 3;
-    int32_t *slot = a.arena + base + static_cast<unsigned long long>(excl + shift) + d.n_prefix;
-    // (second round) the sentence keeps the slot the first round gave it -- and the ids in it: it is taken up at its
-    // first missing word (a.resume: where that word starts, the ids in front of it, the bound of |score| there)
+    // (second round) the sentence is taken up at its first missing word (a.resume: where that word starts, the ids in front
+    // of it, the bound of |score| there); those n0 ids are where the first round put them (tmp_off) and are copied over
     uint32_t p0 = 0u, n0 = 0u, x0 = 0u;
+    uint64_t src0 = 0;                                              // ... in id units from the arena's start (behind the prefix)
     if (MODE == kWmDyn && mine) {
-      slot = a.arena + a.tmp_off[sid] + d.n_prefix;
+      const uint64_t t = a.tmp_off[sid];
+      src0 = ((t & kTmpOffHalf) ? (t & ~kTmpOffHalf) : (H16 ? 2ull * t : t)) + static_cast<uint64_t>(d.n_prefix);
       const U4 rs = a.resume[sid];
       const float bf0 = wv::bits_to_float(rs.z);
       if (rs.x < l64 && rs.y <= rs.x && bf0 >= 0.f && bf0 < 16777216.f) { p0 = rs.x; n0 = rs.y; x0 = static_cast<uint32_t>(bf0); }
     }
+    // ---- the tile's region of the arena: its sentences' ids back to back in text order, in id units (16-bit ids: 16-bit
+    // units), each sentence behind the one before it -- n_prefix ids, its body, n_suffix ids.  A sentence's body has at
+    // most one id per byte of the normalized form (the bytes + 1; the second round checks it); only the region's used
+    // prefix is written, so neighbouring lanes write -- and CompactKernel reads -- neighbouring bytes.  (Until this layout
+    // every sentence had a slot of (len + 1 + n_extra + 6) & ~3 32-bit entries: a C2 sentence's 56 bytes of ids alone in a
+    // 540-byte slot, about 1.45 cache lines fetched per sentence by the compaction; half-size slots, tried in round 6,
+    // left that count where it was.)
+    const bool fixed = direct && list == nullptr && MODE != kWmDyn;  // (direct first round: the region follows from offs)
+    // (second round: n0 <= p0 -- the resume record is checked so -- so the n0 kept ids + the rest's at most len - p0 + 1
+    // fit len + 1 as well: the region is known without the resume record, and the atomic below does not wait for it)
+    const uint64_t room = !have ? 0ull : static_cast<uint64_t>(n_extra) + ((fixed || mine) ? l64 + 1ull : 0ull);
+    uint64_t rtotal = 0;
+    wave_excl_scan64(room, lane, &rtotal);
+    uint64_t base = 0;                                              // the region's first id unit
+    bool overflow;
+    if (fixed) {
+      // tile t holds sentences [64t, 64t + 64): the regions of the tiles before it hold exactly offs[first] - offs[0] bytes
+      // and first sentences -- no arena_head atomic, no round trip before the slots are known
+      const uint64_t o0 = a.offs[0];
+      base = (static_cast<uint64_t>(wv::shfl(static_cast<uint32_t>(beg >> 32), 0)) << 32 | wv::shfl(static_cast<uint32_t>(beg), 0)) - o0 +
+             static_cast<uint64_t>(first) * static_cast<uint64_t>(1 + n_extra);
+      // (the regions end where arena_head starts: the batch's text must lie within the bytes the call was given)
+      const uint64_t end32 = H16 ? (base + rtotal + 1ull) / 2ull : base + rtotal;
+      overflow = end32 > a.arena_cap || end32 > a.arena_first;
+    } else {
+      const uint64_t need = H16 ? (rtotal + 1ull) / 2ull : rtotal;  // int32 entries
+      unsigned long long b32 = 0;
+      if (lane == 0 && rtotal > 0) b32 = wv::atomic_add(a.arena_head, static_cast<unsigned long long>(need + 3ull));
+      b32 = (static_cast<unsigned long long>(wv::shfl(static_cast<uint32_t>(b32 >> 32), 0)) << 32) |
+            wv::shfl(static_cast<uint32_t>(b32), 0);
+      overflow = b32 + need + 3ull > a.arena_cap;
+      b32 = (b32 + 3ull) & ~3ull;
+      base = H16 ? 2ull * b32 : b32;
+    }
+    if (overflow && lane == 0) wv::atomic_or(a.status, kStArenaOverflow);
+    const uint64_t rend = base + rtotal;
+    // where sentence j's body (behind the n0 ids it keeps) starts once every sentence before it has its ids: base + j *
+    // n_extra + n_prefix + (the n0 of sentences 0 .. j) + the ids this round gives the sentences before j.  The last term
+    // is each word's running UNSEGMENTED sum of ids over the tile (stage B), so a word's place is sbase[j] + that sum.
+    const uint64_t sbase = base + static_cast<uint64_t>(lane) * static_cast<uint64_t>(n_extra) + static_cast<uint64_t>(d.n_prefix) +
+                           wv::scan_add(n0);
     const bool work = mine && !overflow;
     const uint32_t len = work ? static_cast<uint32_t>(l64) - p0 : 0u;
     beg += p0;
@@ -187,8 +220,7 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
     {
       const uint32_t start = pu * 16u + begmod;
       const uint64_t ua = tbase + beg - begmod;                    // address of the unit that holds the sentence's first byte
-      const uint64_t so = static_cast<uint64_t>(slot - a.arena);
-      sent[lane] = U4{start, start + len, static_cast<uint32_t>(so), static_cast<uint32_t>(so >> 32)};
+      sent[lane] = U4{start, start + len, static_cast<uint32_t>(sbase), static_cast<uint32_t>(sbase >> 32)};
       sent_ua[lane] = U2{static_cast<uint32_t>(ua), static_cast<uint32_t>(ua >> 32)};
       s_nids[lane] = n0;
       s_stat[lane] = 0u;
@@ -255,6 +287,7 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
     SA.cnt = 0u; SB.cnt = 0u;
     // what the sentence that continues from the previous 64 words has behind it
     uint32_t carry_j = 0xFFFFFFFFu, carry_x = 0u, carry_n = 0u, carry_unk = 0u;
+    uint32_t carry_t = 0u;                                          // ids of the tile's words so far (unsegmented)
     unsigned long long steps = 0;
 
     // stage A: the words' records, windows, lengths, keys; the LDS table's answer; every other word asks `uall`.
@@ -447,6 +480,10 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
       const uint32_t packed = (x << 12) | cnt;
       const uint32_t Sc = wv::scan_add(packed);
       const uint32_t E = Sc - packed;
+      // (the low 12 bits of the same scan, unsegmented: the word's place in the tile's id stream -- at most 64 x 16 ids a
+      // batch, no carry into the bound's bits)
+      const uint32_t T = carry_t + (E & 0xFFFu);
+      carry_t += wv::read_lane(Sc, 63) & 0xFFFu;
       const uint32_t hE = wv::scan_max(head ? E : 0u);
       const uint32_t rel = E - hE;
       uint32_t xb = rel >> 12, nb = rel & 0xFFFu;
@@ -466,16 +503,17 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
       if (word && hit && !(xb < (1u << 24) && static_cast<float>(xb) < lim)) gone = true;
       const U4 sj = sent[j];                                         // {start, end, arena slot}
       if (MODE == kWmDyn && word && hit && nb + cnt > sj.y - sj.x + 1u + n0j) gone = true;   // (more ids than the slot holds: byte fallback of a finely split word)
+      // ---- ids: at the word's place in the tile's stream ----
+      const uint64_t so = (static_cast<uint64_t>(sj.w) << 32 | sj.z) + T;
+      if (word && hit && so + cnt > rend) gone = true;              // (behind a sentence that was given up with more ids than bytes)
       const bool emit = word && hit && !gone;
-      // ---- ids ----
-      const uint64_t so = static_cast<uint64_t>(sj.w) << 32 | sj.z;
       if (emit && !hitd) {
         if (H16) {
-          uint16_t *q = reinterpret_cast<uint16_t *>(a.arena + so) + nb;
+          uint16_t *q = reinterpret_cast<uint16_t *>(a.arena) + so;
           q[0] = static_cast<uint16_t>(id0);
           if (cnt == 2u) q[1] = static_cast<uint16_t>(id1);
         } else {
-          int32_t *q = a.arena + so + nb;
+          int32_t *q = a.arena + so;
           q[0] = static_cast<int32_t>(id0);
           if (cnt == 2u) q[1] = static_cast<int32_t>(id1);
         }
@@ -493,8 +531,8 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
           if (t >= maxc) break;
           if (emit && hitd && t < cnt) {
             const uint32_t id = skip ? idc(t + 1u) : idc(t);
-            if (H16) reinterpret_cast<uint16_t *>(a.arena + so)[nb + t] = static_cast<uint16_t>(id);
-            else (a.arena + so)[nb + t] = static_cast<int32_t>(id);
+            if (H16) reinterpret_cast<uint16_t *>(a.arena)[so + t] = static_cast<uint16_t>(id);
+            else a.arena[so + t] = static_cast<int32_t>(id);
           }
         }
       }
@@ -591,19 +629,63 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
     // ---- per sentence: done, kept for the second round, or handed on ----
     const uint32_t st = s_stat[lane];
     const int n = static_cast<int>(s_nids[lane]);
-    const bool done = work && st == 0u;
+    // the sentence's place: behind the n_extra + ids of every sentence before it (a sentence's count includes the n0 ids it
+    // kept, and ids of words it was given up at: dead ids, never read -- the compaction follows tmp_off and counts)
+    const uint64_t sstart = base + static_cast<uint64_t>(lane) * static_cast<uint64_t>(n_extra) +
+                            static_cast<uint64_t>(wv::scan_add(static_cast<uint32_t>(n)) - static_cast<uint32_t>(n));
+    const bool done = work && st == 0u && sstart + static_cast<uint64_t>(n + n_extra) <= rend;
+    const unsigned long long toff = H16 ? (kTmpOffHalf | sstart) : sstart;   // (tmp_off: id units, kTmpOffHalf for 16-bit ids)
     if (done) {
       if (H16) {
-        uint16_t *s16 = reinterpret_cast<uint16_t *>(slot);
-        for (int x = 0; x < d.n_prefix; ++x) s16[x - d.n_prefix] = static_cast<uint16_t>(d.prefix_ids[x]);
-        for (int x = 0; x < d.n_suffix; ++x) s16[n + x] = static_cast<uint16_t>(d.suffix_ids[x]);
-        a.tmp_off[sid] = kTmpOffHalf | (2ull * static_cast<unsigned long long>(slot - a.arena) - static_cast<unsigned long long>(d.n_prefix));
+        uint16_t *s16 = reinterpret_cast<uint16_t *>(a.arena) + sstart;
+        for (int x = 0; x < d.n_prefix; ++x) s16[x] = static_cast<uint16_t>(d.prefix_ids[x]);
+        for (int x = 0; x < d.n_suffix; ++x) s16[d.n_prefix + n + x] = static_cast<uint16_t>(d.suffix_ids[x]);
       } else {
-        for (int x = 0; x < d.n_prefix; ++x) slot[x - d.n_prefix] = d.prefix_ids[x];
-        for (int x = 0; x < d.n_suffix; ++x) slot[n + x] = d.suffix_ids[x];
-        a.tmp_off[sid] = static_cast<unsigned long long>(slot - d.n_prefix - a.arena);
+        int32_t *s32 = a.arena + sstart;
+        for (int x = 0; x < d.n_prefix; ++x) s32[x] = d.prefix_ids[x];
+        for (int x = 0; x < d.n_suffix; ++x) s32[d.n_prefix + n + x] = d.suffix_ids[x];
       }
+      a.tmp_off[sid] = toff;
       a.counts[sid] = static_cast<uint32_t>(n + n_extra);
+    }
+    if (MODE == kWmDyn) {
+      // (second round) the n0 ids the done sentences kept, from the first round's place to theirs, by the whole wave: the
+      // tile's runs as one stream of ids, id k to lane k % 64 (its sentence by a search over the runs' starts), four ids a
+      // lane loaded before any is stored -- a lane copying its own run would wait out a round trip per id
+      const uint32_t cn = done ? n0 : 0u;
+      const uint32_t ci = wv::scan_add(cn);
+      const uint32_t cx = ci - cn;                                  // where this lane's run starts in the stream
+      const uint32_t ctot = wv::read_lane(ci, 63);
+      const uint64_t dst0 = sstart + static_cast<uint64_t>(d.n_prefix);
+      for (uint32_t k0 = 0; k0 < ctot; k0 += 256u) {
+        uint32_t v[4];
+        uint64_t to[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u) {
+          const uint32_t k = k0 + 64u * u + static_cast<uint32_t>(lane);
+          int lo = 0;                                               // the last run that starts at or before k
+#pragma unroll
+          for (int step = 32; step >= 1; step >>= 1) {
+            const uint32_t pv = wv::shfl(cx, lo + step);
+            if (pv <= k) lo += step;
+          }
+          const uint32_t r = k - wv::shfl(cx, lo);
+          const uint64_t from = (static_cast<uint64_t>(wv::shfl(static_cast<uint32_t>(src0 >> 32), lo)) << 32 |
+                                 wv::shfl(static_cast<uint32_t>(src0), lo)) + r;
+          to[u] = (static_cast<uint64_t>(wv::shfl(static_cast<uint32_t>(dst0 >> 32), lo)) << 32 |
+                   wv::shfl(static_cast<uint32_t>(dst0), lo)) + r;
+          v[u] = 0u;
+          if (k < ctot) v[u] = H16 ? reinterpret_cast<const uint16_t *>(a.arena)[from] : static_cast<uint32_t>(a.arena[from]);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u) {
+          const uint32_t k = k0 + 64u * u + static_cast<uint32_t>(lane);
+          if (k < ctot) {
+            if (H16) reinterpret_cast<uint16_t *>(a.arena)[to[u]] = static_cast<uint16_t>(v[u]);
+            else a.arena[to[u]] = static_cast<int32_t>(v[u]);
+          }
+        }
+      }
     }
     const bool left = have && !done;
     if (left) a.counts[sid] = 0u;                    // (until a later pass has had it)
@@ -620,7 +702,7 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
     if (MODE == kWmCollect) {
       const bool again = left && work && st == kWwAgain;
       const bool gonel = left && !again;
-      if (again) a.tmp_off[sid] = static_cast<unsigned long long>(slot - d.n_prefix - a.arena);
+      if (again) a.tmp_off[sid] = toff;                             // (the second round copies the ids in front of its resume point)
       const uint32_t ca = direct ? 0u : c;
       append_lanes(wv::ballot(again), again, sid, a.left_lists + static_cast<uint64_t>(ca) * a.n, &a.left_counts[ca], lane);
       hand_on(gonel, a.left2_lists, a.left2_counts);
