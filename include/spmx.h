@@ -163,6 +163,70 @@ int spmx_rccl_comm_init(void **nccl_comm, int world, int rank, const void *id128
 int spmx_rccl_comm_destroy(void *nccl_comm);
 const char *spmx_gather_last_error(void);
 
+/* ---- the packed gather: the same result from 16-bit ids and byte counts, with no host synchronisation per step ---------
+ * spmx_all_gather_ids above moves int32 ids and uint64 offsets and reads the counts back in every call.  This form agrees
+ * capacities ONCE (spmx_gather_plan_create, collective, the only place that synchronises), and then every step is
+ * pack kernel -> transfer of equal-sized blocks -> unpack kernel, all stream-ordered: the number of ids is read on the device,
+ * errors are found on the device and wait there until spmx_gather_plan_status asks.
+ *
+ * WIRE BLOCK, version 1 (one per rank; little endian; every section starts at a multiple of 128 bytes that follows from the
+ * agreed capacities alone, so all blocks of a plan have one size and one layout -- spmx_packed_block_bytes):
+ *   header  16 uint64: [0] 1 | 0x58504B31 << 32 (format version, magic)   [1] sentences   [2] ids
+ *           [3] id width (2: piece_size <= 65536, else 4) | count width << 8 (1: max_ids_per_sentence <= 255, 2: <= 65535, else 4)
+ *           [4] status bits, 0 = valid: 1 sentences over the agreed capacity, 2 ids over it, 4 a count outside the count
+ *               width, 8 an id outside the id width, 16 a null buffer with a non-zero size.  A block with a status carries NO
+ *               sentences: [1] / [2] then say what the sender was asked to pack, the payload is undefined.
+ *           [5] [6] capacities of the sender's own d_all_ids / d_all_id_offsets   [7] [8] the agreed max_sentences / max_ids
+ *   bases   per tile of 256 sentences the rank-local id offset at the tile's start, uint64: the receiver rebuilds the offsets
+ *           of a tile from this and a scan over the tile's 256 counts alone
+ *   counts  ids per sentence, count-width bytes each
+ *   ids     id-width bytes each
+ * Header, bases and alignment cost at most max_sentences / 32 + 520 bytes.  A block is padded to the agreed capacities and
+ * travels whole: agree TIGHT capacities (byte-balanced shards differ by a few per cent; a capacity of twice the need doubles
+ * the traffic).  A later version (a code shorter than 16 bits per id) announces itself in header word 0.
+ *
+ * Status of a gather (d_status of spmx_unpack_ids; inside a plan): 4 uint64 -- [0] 0 or the StatusCode number (8: a shard
+ * over the agreed capacity, or the gathered CSR over some rank's output capacity; 11: a count or an id outside its width;
+ * 3: a null buffer; 13: not a block of this version and these capacities), [1] the rank it names (0xFFFFFFFF: the caller's
+ * own output buffers, spmx_unpack_ids only), [2] the status bits (32: output capacity, 64: format), [3] ids in the valid
+ * blocks.  With a non-zero status the unpack writes NOTHING else: not the CSR, not the prefix sums.  Every rank decides from
+ * the same world headers, so every rank gets the same answer and none is left waiting in a transfer. */
+typedef struct spmx_gather_plan spmx_gather_plan;
+/* Collective, ONCE: agrees MAX over the ranks of max_sentences, max_ids, max_ids_per_sentence and piece_size (one all-gather
+ * of four words, read back), allocates world blocks on the current device.  Host-side errors (3, 13, 14) as above. */
+int spmx_gather_plan_create(void *nccl_comm, int rank, int world, uint32_t piece_size, uint64_t max_sentences,
+                            uint64_t max_ids, uint64_t max_ids_per_sentence, spmx_gather_plan **plan);
+uint64_t spmx_gather_plan_block_bytes(const spmx_gather_plan *plan);
+/* Stream-ordered, collective.  d_ids / d_id_offsets: the rank's CSR as spmx_encode_batch_device wrote it (the ids of the
+ * shard are d_ids[d_id_offsets[0] .. d_id_offsets[n_sentences])).  Outputs as spmx_all_gather_ids, except that the prefix
+ * sums d_rank_sentences / d_rank_ids (world + 1 entries each, nullable) are DEVICE memory.  Returns 0 when everything was
+ * queued (3 / 13 / 14: a host-side failure); what the device found is spmx_gather_plan_status's to tell.  No read-back, no
+ * stream synchronisation: a caller overlaps the gather with the next encode by giving it a stream of its own. */
+int spmx_all_gather_ids_packed(spmx_gather_plan *plan, const int32_t *d_ids, const uint64_t *d_id_offsets,
+                               uint64_t n_sentences, int32_t *d_all_ids, uint64_t all_ids_capacity,
+                               uint64_t *d_all_id_offsets, uint64_t all_offsets_capacity, uint64_t *d_rank_sentences,
+                               uint64_t *d_rank_ids, void *stream);
+/* Synchronises `stream` and returns the status of the last gather queued on it: 0, or the StatusCode with the rank named
+ * in spmx_gather_last_error().  The same on every rank.  A plan stays usable after a failed gather. */
+int spmx_gather_plan_status(spmx_gather_plan *plan, void *stream);
+void spmx_gather_plan_destroy(spmx_gather_plan *plan);
+/* The two halves on their own -- for hosts with a transport of their own (MPI, torch.distributed), and for device -> host
+ * copies of ids at about half the bytes.  No RCCL, no communicator; the caller passes the agreed numbers to every call.
+ * d_block / d_blocks: device memory aligned to 128 bytes, spmx_packed_block_bytes(...) bytes per rank, the blocks of
+ * spmx_unpack_ids back to back in rank order.  all_ids_capacity / all_offsets_capacity of spmx_pack_ids: what this rank's
+ * unpack outputs will hold (they travel in the header; UINT64_MAX where every rank sizes its outputs alike).  d_status: 4
+ * uint64 of device memory, written by every unpack; spmx_packed_status(host copy of them) turns them into the StatusCode and
+ * the message of spmx_gather_last_error().  Both calls are stream-ordered and never synchronise. */
+uint64_t spmx_packed_block_bytes(uint32_t piece_size, uint64_t max_sentences, uint64_t max_ids, uint64_t max_ids_per_sentence);
+int spmx_pack_ids(const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n_sentences, uint32_t piece_size,
+                  uint64_t max_sentences, uint64_t max_ids, uint64_t max_ids_per_sentence, uint64_t all_ids_capacity,
+                  uint64_t all_offsets_capacity, void *d_block, void *stream);
+int spmx_unpack_ids(const void *d_blocks, int world, uint32_t piece_size, uint64_t max_sentences, uint64_t max_ids,
+                    uint64_t max_ids_per_sentence, int32_t *d_all_ids, uint64_t all_ids_capacity, uint64_t *d_all_id_offsets,
+                    uint64_t all_offsets_capacity, uint64_t *d_rank_sentences, uint64_t *d_rank_ids, uint64_t *d_status,
+                    void *stream);
+int spmx_packed_status(const uint64_t *status4);
+
 /* Single sentence, caller-provided buffer (Encode(input, &ids)): returns the sentence's own Status, as the
  * reference does.  RESOURCE_EXHAUSTED with the needed size in *n_ids if cap is too small. */
 int spmx_encode(spmx_handle *h, const char *text, uint64_t len, int32_t *ids, uint64_t cap, uint64_t *n_ids);

@@ -361,6 +361,40 @@ class SentencePieceProcessor {
     if (rc == 0) return util::Status();
     return util::Status(static_cast<util::StatusCode>(rc), spmx_gather_last_error());
   }
+  // The packed form of the same gather (spmx_gather_plan_*, spmx_all_gather_ids_packed): 16-bit ids where the vocabulary
+  // allows, one- or two-byte counts, and no host synchronisation per step.  Create() is collective and agrees the
+  // capacities ONCE (pass piece_size = GetPieceSize(), and tight maxima: blocks travel padded to them); AllGatherIds()
+  // only queues work on `stream` -- the prefix sums d_rank_sentences / d_rank_ids (world + 1 entries, nullable) are
+  // DEVICE memory -- and what the device found (a shard over the agreed capacities, a count or id outside its width, an
+  // output buffer too small on some rank) is LastStatus()'s to tell, the same on every rank, after it synchronised `stream`.
+  class PackedGatherPlan {
+   public:
+    PackedGatherPlan() = default;
+    PackedGatherPlan(const PackedGatherPlan &) = delete;
+    PackedGatherPlan &operator=(const PackedGatherPlan &) = delete;
+    ~PackedGatherPlan() { spmx_gather_plan_destroy(plan_); }
+    util::Status Create(void *comm, int rank, int world, uint32_t piece_size, uint64_t max_sentences, uint64_t max_ids,
+                        uint64_t max_ids_per_sentence) {
+      spmx_gather_plan_destroy(plan_);
+      plan_ = nullptr;
+      return FromGather(spmx_gather_plan_create(comm, rank, world, piece_size, max_sentences, max_ids, max_ids_per_sentence, &plan_));
+    }
+    uint64_t BlockBytes() const { return spmx_gather_plan_block_bytes(plan_); }
+    util::Status AllGatherIds(const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n_sentences, int32_t *d_all_ids,
+                              uint64_t all_ids_capacity, uint64_t *d_all_id_offsets, uint64_t all_offsets_capacity,
+                              uint64_t *d_rank_sentences, uint64_t *d_rank_ids, void *stream) {
+      return FromGather(spmx_all_gather_ids_packed(plan_, d_ids, d_id_offsets, n_sentences, d_all_ids, all_ids_capacity,
+                                                   d_all_id_offsets, all_offsets_capacity, d_rank_sentences, d_rank_ids, stream));
+    }
+    util::Status LastStatus(void *stream) { return FromGather(spmx_gather_plan_status(plan_, stream)); }
+
+   private:
+    static util::Status FromGather(int rc) {
+      if (rc == 0) return util::Status();
+      return util::Status(static_cast<util::StatusCode>(rc), spmx_gather_last_error());
+    }
+    spmx_gather_plan *plan_ = nullptr;
+  };
 
   // ---- pieces / SentencePieceText (sentencepiece_processor.h:295-296, :401-402, :453-456) ----
   // The device returns ids, input spans and normalized-text spans (spmx_encode_batch_spans) and the normalized text

@@ -32,7 +32,7 @@ namespace {
 
 // the part of rccl.h this file needs (ncclResult_t 0 = ncclSuccess; ncclDataType_t numbers: rccl.h:459-470)
 struct NcclUniqueId { char internal[128]; };
-enum { kNcclInt32 = 2, kNcclUint64 = 5 };
+enum { kNcclInt8 = 0, kNcclInt32 = 2, kNcclUint64 = 5 };
 struct RcclApi {
   int (*GetUniqueId)(NcclUniqueId *) = nullptr;
   int (*CommInitRank)(void **, int, NcclUniqueId, int) = nullptr;
@@ -93,6 +93,94 @@ int FailG(int code, const std::string &msg) {
   } while (0)
 
 }  // namespace
+
+#ifdef SPMX_EMULATED
+// The CPU model of the wavefront (tests/emu) has no kernels.hip: the two launchers of the packed gather run their device
+// bodies over the grid there, one workgroup of one wavefront after another.
+namespace spmx {
+hipError_t LaunchPackIds(const PackArgs &a, int grid, hipStream_t) {
+  for (int b = 0; b < grid; ++b) emu::RunWave(b, grid, nullptr, [&] { pack_block(a); });
+  return hipSuccess;
+}
+hipError_t LaunchUnpackIds(const UnpackArgs &a, int grid, hipStream_t) {
+  for (int b = 0; b < grid; ++b) emu::RunWave(b, grid, nullptr, [&] { unpack_block(a); });
+  return hipSuccess;
+}
+}  // namespace spmx
+constexpr uint64_t kPackedMaxGrid = 3;
+#else
+constexpr uint64_t kPackedMaxGrid = 8192;    // workgroups of one wavefront: 32 per CU of an MI355X in flight
+#endif
+
+namespace {
+
+// workgroups for a streaming pass over `sentences` (a tile each) and `ids` (64 units each)
+int PackedGrid(uint64_t sentences, uint64_t ids) {
+  const uint64_t t = (sentences + kPackedTile - 1) / kPackedTile, g = (ids + 64 * kPackedUnit - 1) / (64 * kPackedUnit);
+  const uint64_t m = t > g ? t : g;
+  return static_cast<int>(m < 1 ? 1 : (m > kPackedMaxGrid ? kPackedMaxGrid : m));
+}
+
+int PackInto(const PackedLayout &lay, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, uint64_t out_cap_ids,
+             uint64_t out_cap_offs, uint8_t *d_block, hipStream_t stream) {
+  PackArgs pa{};
+  pa.ids = d_ids;
+  pa.offs = d_id_offsets;
+  pa.n = n;
+  pa.block = d_block;
+  pa.lay = lay;
+  pa.out_cap_ids = out_cap_ids;
+  pa.out_cap_offs = out_cap_offs;
+  pa.bad_args = n && !d_id_offsets ? 1u : 0u;
+  HIPG_OR_RETURN(hipMemsetAsync(d_block, 0, kPhWords * 8, stream));     // (the status word: the kernel only ORs into it)
+  HIPG_OR_RETURN(LaunchPackIds(pa, PackedGrid(n < lay.cap_s ? n : lay.cap_s, lay.cap_i), stream));
+  return 0;
+}
+
+int UnpackFrom(const PackedLayout &lay, const uint8_t *d_blocks, int world, int32_t *d_all_ids, uint64_t all_ids_capacity,
+               uint64_t *d_all_id_offsets, uint64_t all_offsets_capacity, uint64_t *d_rank_sentences, uint64_t *d_rank_ids,
+               uint64_t *d_status, hipStream_t stream) {
+  UnpackArgs ua{};
+  ua.blocks = d_blocks;
+  ua.block_stride = lay.bytes;
+  ua.world = static_cast<uint32_t>(world);
+  ua.lay = lay;
+  ua.all_ids = d_all_ids;
+  ua.all_offs = d_all_id_offsets;
+  ua.cap_ids = all_ids_capacity;
+  ua.cap_offs = all_offsets_capacity;
+  ua.rank_sentences = d_rank_sentences;
+  ua.rank_ids = d_rank_ids;
+  ua.status = d_status;
+  const uint64_t w = static_cast<uint64_t>(world);
+  HIPG_OR_RETURN(LaunchUnpackIds(ua, PackedGrid(lay.cap_s * w, lay.cap_i * w), stream));
+  return 0;
+}
+
+std::string PackedMessage(const uint64_t st[4]) {
+  const uint32_t bits = static_cast<uint32_t>(st[2]);
+  const std::string who = st[1] == 0xFFFFFFFFu ? std::string("this caller") : "rank " + std::to_string(st[1]);
+  std::string what;
+  if (bits & kPsFormat) what = "'s block is not a packed block of this version and these capacities";
+  else if (bits & kPsArgs) what = " passed a null id / offset buffer with a non-zero size";
+  else if (bits & kPsSentences) what = " has more sentences than the agreed capacity";
+  else if (bits & kPsIds) what = " has more ids than the agreed capacity";
+  else if (bits & kPsOutput) what = "'s output buffers are too small for the gathered CSR (" + std::to_string(st[3]) + " ids)";
+  else if (bits & kPsCount) what = " has a sentence with more ids than the agreed count width holds";
+  else if (bits & kPsId) what = " has an id outside the agreed id width";
+  return who + what + " (every rank sees this: nothing was written)";
+}
+
+}  // namespace
+
+struct spmx_gather_plan {
+  void *comm = nullptr;
+  int rank = 0, world = 1;
+  PackedLayout lay{};
+  uint8_t *d_blocks = nullptr;     // world blocks; [rank] is the one this rank packs into and sends from
+  uint64_t *d_status = nullptr;    // what the last unpack found (UnpackArgs::status)
+  uint64_t *h_status = nullptr;    // pinned: where spmx_gather_plan_status reads it
+};
 
 constexpr int kGatherWords = 5;      // per rank in the counts all-gather: sentences, ids, id capacity, offset capacity, arguments valid
 
@@ -195,6 +283,143 @@ int spmx_all_gather_ids(void *nccl_comm, int rank, int world, const int32_t *d_i
   if (grid > 2048) grid = 2048;
   HIPG_OR_RETURN(LaunchRebase(ra, static_cast<int>(grid), stream));
   return 0;
+}
+
+// ---- the packed gather: 16-bit ids, byte counts, no host synchronisation in the steady state ----
+// Transfer: the blocks have ONE size, so an ncclAllGather of bytes would do; the grouped, staggered ncclSend / ncclRecv of
+// spmx_all_gather_ids is kept instead -- every rank packs straight into its own slot of the receive array and the unpack
+// kernel reads it there, so there is no copy of the rank's own block (an out-of-place all-gather makes one, 1 / world of the
+// traffic of a step; an in-place one ties the send buffer to the receive array the same way but leaves the peer order to
+// the library), and world - 1 concurrent point-to-point transfers is the pattern a fully connected xGMI node is built for.
+
+uint64_t spmx_packed_block_bytes(uint32_t piece_size, uint64_t max_sentences, uint64_t max_ids, uint64_t max_ids_per_sentence) {
+  return MakePackedLayout(piece_size, max_sentences, max_ids, max_ids_per_sentence).bytes;
+}
+
+int spmx_pack_ids(const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n_sentences, uint32_t piece_size,
+                  uint64_t max_sentences, uint64_t max_ids, uint64_t max_ids_per_sentence, uint64_t all_ids_capacity,
+                  uint64_t all_offsets_capacity, void *d_block, void *stream) {
+  if (!d_block || (reinterpret_cast<uintptr_t>(d_block) & 127u)) return FailG(3, "the block must be device memory aligned to 128 bytes");
+  return PackInto(MakePackedLayout(piece_size, max_sentences, max_ids, max_ids_per_sentence), d_ids, d_id_offsets, n_sentences,
+                  all_ids_capacity, all_offsets_capacity, static_cast<uint8_t *>(d_block), static_cast<hipStream_t>(stream));
+}
+
+int spmx_unpack_ids(const void *d_blocks, int world, uint32_t piece_size, uint64_t max_sentences, uint64_t max_ids,
+                    uint64_t max_ids_per_sentence, int32_t *d_all_ids, uint64_t all_ids_capacity, uint64_t *d_all_id_offsets,
+                    uint64_t all_offsets_capacity, uint64_t *d_rank_sentences, uint64_t *d_rank_ids, uint64_t *d_status,
+                    void *stream) {
+  if (world < 1 || world > kMaxRanks) return FailG(3, "world must be 1 .. 64");
+  if (!d_blocks || (reinterpret_cast<uintptr_t>(d_blocks) & 127u) || !d_status)
+    return FailG(3, "the blocks must be device memory aligned to 128 bytes, the status words not null");
+  return UnpackFrom(MakePackedLayout(piece_size, max_sentences, max_ids, max_ids_per_sentence), static_cast<const uint8_t *>(d_blocks),
+                    world, d_all_ids, all_ids_capacity, d_all_id_offsets, all_offsets_capacity, d_rank_sentences, d_rank_ids,
+                    d_status, static_cast<hipStream_t>(stream));
+}
+
+int spmx_packed_status(const uint64_t *status4) {
+  if (!status4) return FailG(3, "null status words");
+  const int code = static_cast<int>(status4[0]);
+  if (code == 0) { t_gather_error.clear(); return 0; }
+  return FailG(code, PackedMessage(status4));
+}
+
+int spmx_gather_plan_create(void *nccl_comm, int rank, int world, uint32_t piece_size, uint64_t max_sentences,
+                            uint64_t max_ids, uint64_t max_ids_per_sentence, spmx_gather_plan **plan) {
+  RcclApi &api = Rccl();
+  if (!api.ok) return FailG(14, api.error);
+  if (world < 1 || world > kMaxRanks || rank < 0 || rank >= world) return FailG(3, "world must be 1 .. 64 and rank inside it");
+  if (!nccl_comm || !plan) return FailG(3, "null communicator or plan pointer");
+  *plan = nullptr;
+  // ---- the agreement: MAX over the ranks, through device memory (the one read-back of this interface) ----
+  constexpr int kWords = 4;
+  const uint64_t mine[kWords] = {max_sentences, max_ids, max_ids_per_sentence, piece_size};
+  uint64_t got[kWords * kMaxRanks];
+  uint64_t *d_words = nullptr;
+  HIPG_OR_RETURN(hipMalloc(reinterpret_cast<void **>(&d_words), sizeof(uint64_t) * kWords * static_cast<size_t>(1 + world)));
+  int rc = 0;
+  auto agree = [&]() -> int {
+    HIPG_OR_RETURN(hipMemcpyAsync(d_words, mine, sizeof(mine), hipMemcpyHostToDevice, nullptr));
+    RCCL_OR_RETURN(api, api.AllGather(d_words, d_words + kWords, kWords, kNcclUint64, nccl_comm, nullptr));
+    HIPG_OR_RETURN(hipMemcpyAsync(got, d_words + kWords, sizeof(uint64_t) * kWords * static_cast<size_t>(world), hipMemcpyDeviceToHost, nullptr));
+    HIPG_OR_RETURN(hipStreamSynchronize(nullptr));
+    return 0;
+  };
+  rc = agree();
+  (void)hipFree(d_words);
+  if (rc != 0) return rc;
+  uint64_t agreed[kWords] = {0, 0, 0, 0};
+  for (int r = 0; r < world; ++r)
+    for (int k = 0; k < kWords; ++k)
+      if (got[kWords * r + k] > agreed[k]) agreed[k] = got[kWords * r + k];
+  spmx_gather_plan *p = new spmx_gather_plan;
+  p->comm = nccl_comm;
+  p->rank = rank;
+  p->world = world;
+  p->lay = MakePackedLayout(agreed[3] > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(agreed[3]), agreed[0], agreed[1], agreed[2]);
+  auto allocate = [&]() -> int {
+    HIPG_OR_RETURN(hipMalloc(reinterpret_cast<void **>(&p->d_blocks), p->lay.bytes * static_cast<size_t>(world)));
+    HIPG_OR_RETURN(hipMalloc(reinterpret_cast<void **>(&p->d_status), 4 * sizeof(uint64_t)));
+    HIPG_OR_RETURN(hipHostMalloc(reinterpret_cast<void **>(&p->h_status), 4 * sizeof(uint64_t), hipHostMallocDefault));
+    HIPG_OR_RETURN(hipMemset(p->d_status, 0, 4 * sizeof(uint64_t)));
+    return 0;
+  };
+  rc = allocate();
+  if (rc != 0) { spmx_gather_plan_destroy(p); return rc; }
+  *plan = p;
+  return 0;
+}
+
+uint64_t spmx_gather_plan_block_bytes(const spmx_gather_plan *plan) { return plan ? plan->lay.bytes : 0u; }
+
+int spmx_all_gather_ids_packed(spmx_gather_plan *plan, const int32_t *d_ids, const uint64_t *d_id_offsets,
+                               uint64_t n_sentences, int32_t *d_all_ids, uint64_t all_ids_capacity,
+                               uint64_t *d_all_id_offsets, uint64_t all_offsets_capacity, uint64_t *d_rank_sentences,
+                               uint64_t *d_rank_ids, void *stream_) {
+  RcclApi &api = Rccl();
+  if (!api.ok) return FailG(14, api.error);
+  if (!plan) return FailG(3, "null plan");            // (the only error decided by one rank alone)
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const PackedLayout &lay = plan->lay;
+  const int world = plan->world, rank = plan->rank;
+  uint8_t *mine = plan->d_blocks + lay.bytes * static_cast<size_t>(rank);
+  // Everything a rank could object to -- its shard against the agreed capacities, its ids and counts against the widths, a
+  // null buffer, its output capacities -- travels in its block's header, so every rank goes through the same transfers
+  // whatever it was given, and every rank's unpack kernel takes the same decision from the same world headers.
+  int rc = PackInto(lay, d_ids, d_id_offsets, n_sentences, d_all_ids ? all_ids_capacity : 0u, d_all_id_offsets ? all_offsets_capacity : 0u,
+                    mine, stream);
+  if (rc != 0) return rc;
+  if (world > 1) {
+    RCCL_OR_RETURN(api, api.GroupStart());
+    int in_group = 0;
+    for (int k = 1; k < world && in_group == 0; ++k) {
+      const int to = (rank + k) % world, from = (rank - k + world) % world;    // (every rank a different peer per step)
+      in_group = api.Send(mine, lay.bytes, kNcclInt8, to, plan->comm, stream);
+      if (in_group == 0) in_group = api.Recv(plan->d_blocks + lay.bytes * static_cast<size_t>(from), lay.bytes, kNcclInt8, from, plan->comm, stream);
+    }
+    const int ended = api.GroupEnd();
+    if (in_group != 0) return FailG(13, std::string("ncclSend / ncclRecv: ") + (api.GetErrorString ? api.GetErrorString(in_group) : "RCCL error"));
+    RCCL_OR_RETURN(api, ended);
+  }
+  return UnpackFrom(lay, plan->d_blocks, world, d_all_ids, all_ids_capacity, d_all_id_offsets, all_offsets_capacity, d_rank_sentences,
+                    d_rank_ids, plan->d_status, stream);
+}
+
+int spmx_gather_plan_status(spmx_gather_plan *plan, void *stream_) {
+  if (!plan) return FailG(3, "null plan");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  HIPG_OR_RETURN(hipMemcpyAsync(plan->h_status, plan->d_status, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIPG_OR_RETURN(hipStreamSynchronize(stream));
+  const int code = static_cast<int>(plan->h_status[0]);
+  if (code == 0) { t_gather_error.clear(); return 0; }
+  return FailG(code, PackedMessage(plan->h_status));
+}
+
+void spmx_gather_plan_destroy(spmx_gather_plan *plan) {
+  if (!plan) return;
+  (void)hipFree(plan->d_blocks);
+  (void)hipFree(plan->d_status);
+  if (plan->h_status) (void)hipHostFree(plan->h_status);
+  delete plan;
 }
 
 }  // extern "C"

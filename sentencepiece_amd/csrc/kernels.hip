@@ -147,6 +147,8 @@ __global__ __launch_bounds__(64) void CompactKernel(CompactArgs a) {
 }
 __global__ __launch_bounds__(64) void CompactBigKernel(CompactArgs a) { compact_big_block(a); }
 __global__ __launch_bounds__(64) void RebaseOffsetsKernel(RebaseArgs a) { rebase_block(a); }
+__global__ __launch_bounds__(64) void PackIdsKernel(PackArgs a) { pack_block(a); }
+__global__ __launch_bounds__(64) void UnpackIdsKernel(UnpackArgs a) { unpack_block(a); }
 
 namespace {
 using EncodeFn = void (*)(EncodeArgs);
@@ -308,6 +310,14 @@ hipError_t LaunchScan(const ScanArgs &a, int grid, hipStream_t stream) {
 
 hipError_t LaunchRebase(const RebaseArgs &a, int grid, hipStream_t stream) {
   hipLaunchKernelGGL(RebaseOffsetsKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t LaunchPackIds(const PackArgs &a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(PackIdsKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t LaunchUnpackIds(const UnpackArgs &a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(UnpackIdsKernel, dim3(grid), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

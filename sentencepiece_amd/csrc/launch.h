@@ -62,6 +62,9 @@ hipError_t LaunchScan(const ScanArgs &a, int grid, hipStream_t stream);
 hipError_t LaunchCompact(const CompactArgs &a, int grid, hipStream_t stream);
 hipError_t LaunchCompactBig(const CompactArgs &a, int grid, hipStream_t stream);   // the document blocks LaunchCompact listed
 hipError_t LaunchRebase(const RebaseArgs &a, int grid, hipStream_t stream);   // kernels_gather.h
+// the packed gather's two streaming kernels (kernels_gather.h pack_block / unpack_block); workgroups of one wavefront
+hipError_t LaunchPackIds(const PackArgs &a, int grid, hipStream_t stream);
+hipError_t LaunchUnpackIds(const UnpackArgs &a, int grid, hipStream_t stream);
 
 }  // namespace spmx
 #endif

@@ -316,3 +316,112 @@ def encode_sharded(encode_fn, text, offsets, dist, device, group=None):
     full_off = torch.cat([offs[r][:-1] + int(bases[r]) for r in range(world)] +
                          [torch.tensor([int(bases[-1])], dtype=offs[0].dtype, device=device)])
     return full_ids, full_off
+
+
+# ---- the packed gather of the C ABI (include/spmx.h: spmx_gather_plan_*, spmx_pack_ids / spmx_unpack_ids) -------------
+# Thin wrappers: the kernels, the wire format and the transfers live in libspmx.so; these only pass tensor pointers.
+
+def _ptr(t):
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None
+
+
+def _check(lib, rc):
+    if rc != 0:
+        raise RuntimeError("packed gather: status %d: %s" % (rc, (lib.spmx_gather_last_error() or b"").decode("utf-8", "replace")))
+
+
+def packed_block_bytes(piece_size, max_sentences, max_ids, max_ids_per_sentence, _lib=None):
+    """Bytes of one rank's wire block under these agreed numbers (no plan needed)."""
+    from . import _capi
+    lib = _lib or _capi.lib()
+    return int(lib.spmx_packed_block_bytes(int(piece_size), int(max_sentences), int(max_ids), int(max_ids_per_sentence)))
+
+
+def pack_ids(ids, id_offsets, piece_size, max_sentences, max_ids, max_ids_per_sentence, out=None,
+             all_ids_capacity=2 ** 64 - 1, all_offsets_capacity=2 ** 64 - 1, _lib=None):
+    """One rank's CSR (int32 ids, int64 / uint64 offsets [n + 1], device tensors) -> its wire block, a uint8 tensor of
+    packed_block_bytes(...) bytes (``out``: a 128-byte aligned one to write into).  Stream-ordered; a shard that breaks the
+    agreed numbers is marked in the block's header and reported by the unpack."""
+    from . import _capi
+    lib = _lib or _capi.lib()
+    n = max(int(id_offsets.numel()) - 1, 0)
+    if out is None:
+        out = torch.empty(packed_block_bytes(piece_size, max_sentences, max_ids, max_ids_per_sentence, lib), dtype=torch.uint8,
+                          device=ids.device)
+    _check(lib, lib.spmx_pack_ids(_ptr(ids), _ptr(id_offsets), n, int(piece_size), int(max_sentences), int(max_ids),
+                                  int(max_ids_per_sentence), int(all_ids_capacity), int(all_offsets_capacity), out.data_ptr(),
+                                  _stream(ids.device)))
+    return out
+
+
+def unpack_ids(blocks, world, piece_size, max_sentences, max_ids, max_ids_per_sentence, all_ids, all_id_offsets,
+               rank_sentences=None, rank_ids=None, status=None, _lib=None):
+    """``blocks``: the world wire blocks back to back in rank order (one uint8 tensor) -> the job's CSR written into
+    ``all_ids`` (int32) / ``all_id_offsets`` (int64, total sentences + 1) and the per-rank prefix sums into
+    ``rank_sentences`` / ``rank_ids`` (int64 [world + 1], optional), all on the device.  Returns the 4-word status tensor
+    (include/spmx.h); ``packed_status(status)`` reads it (that is the synchronisation point)."""
+    from . import _capi
+    lib = _lib or _capi.lib()
+    if status is None:
+        status = torch.zeros(4, dtype=torch.int64, device=blocks.device)
+    _check(lib, lib.spmx_unpack_ids(blocks.data_ptr(), int(world), int(piece_size), int(max_sentences), int(max_ids),
+                                    int(max_ids_per_sentence), _ptr(all_ids), int(all_ids.numel()), _ptr(all_id_offsets),
+                                    int(all_id_offsets.numel()), _ptr(rank_sentences), _ptr(rank_ids), status.data_ptr(),
+                                    _stream(blocks.device)))
+    return status
+
+
+def packed_status(status, _lib=None):
+    """Reads an unpack's status words back (synchronises): raises RuntimeError naming the rank unless they say 0."""
+    from . import _capi
+    lib = _lib or _capi.lib()
+    host = status.cpu().numpy().astype(np.uint64)
+    _check(lib, lib.spmx_packed_status(host.ctypes.data))
+
+
+class PackedGatherer:
+    """The packed all-gather of the C ABI over torch tensors: ``PackedGatherer(comm, rank, world, piece_size,
+    max_sentences, max_ids, max_ids_per_sentence)`` is collective and agrees the capacities once (``comm``: an ncclComm_t
+    as an integer, e.g. from ``spmx_rccl_comm_init``); ``g(ids, id_offsets, all_ids, all_id_offsets, rank_sentences,
+    rank_ids)`` queues pack -> transfer -> unpack on the current stream and returns at once; ``status()`` synchronises and
+    raises if the last gather found a violation (the same on every rank)."""
+
+    def __init__(self, comm, rank, world, piece_size, max_sentences, max_ids, max_ids_per_sentence, _lib=None):
+        import ctypes as C
+        from . import _capi
+        self.lib = _lib or _capi.lib()
+        self.world = int(world)
+        plan = C.c_void_p()
+        _check(self.lib, self.lib.spmx_gather_plan_create(comm, int(rank), int(world), int(piece_size), int(max_sentences),
+                                                          int(max_ids), int(max_ids_per_sentence), C.byref(plan)))
+        self._plan = plan
+
+    @property
+    def block_bytes(self):
+        return int(self.lib.spmx_gather_plan_block_bytes(self._plan))
+
+    def __call__(self, ids, id_offsets, all_ids, all_id_offsets, rank_sentences=None, rank_ids=None):
+        n = max(int(id_offsets.numel()) - 1, 0)
+        self._device = all_ids.device
+        _check(self.lib, self.lib.spmx_all_gather_ids_packed(self._plan, _ptr(ids), _ptr(id_offsets), n, _ptr(all_ids),
+                                                             int(all_ids.numel()), _ptr(all_id_offsets),
+                                                             int(all_id_offsets.numel()), _ptr(rank_sentences), _ptr(rank_ids),
+                                                             _stream(all_ids.device)))
+
+    def status(self):
+        _check(self.lib, self.lib.spmx_gather_plan_status(self._plan, _stream(getattr(self, "_device", torch.device("cpu")))))
+
+    def close(self):
+        if self._plan is not None:
+            self.lib.spmx_gather_plan_destroy(self._plan)
+            self._plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
