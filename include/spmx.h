@@ -264,6 +264,44 @@ int spmx_decode_batch(spmx_handle *h, const int32_t *ids, const uint64_t *id_off
 /* Single sentence, caller-provided buffer (Decode(ids, &text)); RESOURCE_EXHAUSTED with the needed size in *len. */
 int spmx_decode(spmx_handle *h, const int32_t *ids, uint64_t n_ids, char *out, uint64_t cap, uint64_t *len);
 
+/* ---- decode, SentencePieceText form -------------------------------------
+ * What Decode(ids | pieces, SentencePieceText *) fills (src/sentencepiece_processor.cc:766-925), as arrays: the text, and
+ * for every piece of the result its id and the byte range [begin, end) of its surface (SetSurface, .cc:822-828).
+ *   The pieces of sentence s are the entries [piece_offsets[s], piece_offsets[s + 1]) (n + 1 offsets, the first 0), in the
+ *   order after SetDecodeExtraOptions (.cc:819): reversed under `reverse`, the bos / eos ids in front / behind.
+ *   Every piece has a range; a control piece an empty one at the text's length so far.  Of a character made of k byte
+ *   pieces at offset o the first k - 1 get (o, o) and the last (o, o + k); an invalid byte piece gets U+FFFD, (o, o + 3).
+ *   piece_ids: the ids as given, a piece outside the vocabulary (the pieces form) keeps its code -(k + 1).
+ *   span_begin / span_end are uint32 byte offsets relative to the sentence's own text -- the text BEFORE the
+ *   denormalizer: surface = raw_text[raw_offsets[s] + begin, raw_offsets[s] + end).  `text` is the text AFTER the
+ *   denormalizer (.cc:905-907), what spmx_decode_batch returns; the spans are not rebased onto it.
+ *   raw text: a model WITHOUT a denormalizer_spec has one text only.  The device form then writes neither d_raw_text nor
+ *   d_raw_offsets (both may be NULL) and sets *raw_bytes = *total_bytes; the host forms set *raw_text and *raw_offsets to
+ *   NULL.  The surfaces are slices of `text` in that case.
+ * An id outside [0, GetPieceSize()) fails the call as in spmx_decode_batch and nothing is returned.
+ *
+ * Device-resident form.  Capacities: text_capacity bytes, piece_capacity entries in each of d_piece_ids / d_span_begin /
+ * d_span_end, raw_capacity bytes; d_text_offsets, d_piece_offsets, d_raw_offsets hold n + 1 entries.  Returns
+ * RESOURCE_EXHAUSTED (8) if one is too small: *total_pieces is always the number of pieces, *total_bytes / *raw_bytes the
+ * bytes needed as far as the call got (a piece_capacity that is too small is reported before the denormalizer runs).  The
+ * piece outputs are valid whenever piece_capacity sufficed, also if the text did not fit. */
+int spmx_decode_batch_spans_device(spmx_handle *h, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, void *d_text,
+                                   uint64_t text_capacity, uint64_t *d_text_offsets, int32_t *d_piece_ids, uint32_t *d_span_begin,
+                                   uint32_t *d_span_end, uint64_t piece_capacity, uint64_t *d_piece_offsets, void *d_raw_text,
+                                   uint64_t raw_capacity, uint64_t *d_raw_offsets, void *stream, uint64_t *total_bytes,
+                                   uint64_t *total_pieces, uint64_t *raw_bytes);
+/* 1 if the model carries a denormalizer_spec with rules (the raw text outputs are then written), else 0. */
+int spmx_has_denormalizer(const spmx_handle *h);
+/* Host-array form; every output is released with spmx_free(). */
+int spmx_decode_batch_spans(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, char **text,
+                            uint64_t **text_offsets, int32_t **piece_ids, uint32_t **span_begin, uint32_t **span_end,
+                            uint64_t **piece_offsets, char **raw_text, uint64_t **raw_offsets);
+/* The pieces form: ids and literals as spmx_decode_batch_pieces takes them.  The surface of a literal is its own bytes. */
+int spmx_decode_batch_pieces_spans(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n,
+                                   const char *lit_bytes, const uint64_t *lit_offsets, uint64_t n_lit, char **text,
+                                   uint64_t **text_offsets, int32_t **piece_ids, uint32_t **span_begin, uint32_t **span_end,
+                                   uint64_t **piece_offsets, char **raw_text, uint64_t **raw_offsets);
+
 /* ---- spans form ---------------------------------------------------------
  * The ids plus, for every id, the byte range [begin, end) of its sentence that it covers: pieces(i).begin() /
  * .end() of the SentencePieceText that Encode(absl::string_view, SentencePieceText *) fills

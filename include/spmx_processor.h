@@ -688,6 +688,58 @@ class SentencePieceProcessor {
     (void)Decode(pieces, &out);
     return out;
   }
+  // ---- decode to SentencePieceText (sentencepiece_processor.h:306-312, .cc:766-925) ----
+  // text: the decoded text (after the denormalizer, .cc:905-907); per piece, in the order after SetDecodeExtraOptions
+  // (.cc:819), its string, id, surface and the byte range of the surface in the text BEFORE the denormalizer (SetSurface,
+  // .cc:822-828: every piece has all three, an empty surface included).  The ranges come from the decode kernels' spans form
+  // (spmx_decode_batch_spans / spmx_decode_batch_pieces_spans).
+  virtual util::Status Decode(const std::vector<int> &ids, SentencePieceText *spt) const {
+    if (!h_) return status();
+    if (!spt) return util::Status(util::StatusCode::kInternal, "output proto is null");
+    static_assert(sizeof(int) == sizeof(int32_t), "ids are 32-bit");
+    return DecodeSpans(reinterpret_cast<const int32_t *>(ids.data()), ids.size(), nullptr, nullptr, spt);
+  }
+  virtual util::Status Decode(const std::vector<std::string_view> &pieces, SentencePieceText *spt) const {
+    if (!h_) return status();
+    if (!spt) return util::Status(util::StatusCode::kInternal, "output proto is null");
+    const int unk = unk_id();
+    const std::string unk_name = IdToPiece(unk);
+    const bool to_unk = spmx_decode_unk_option(h_) != 0;
+    std::vector<int32_t> ids;
+    std::string lit;
+    std::vector<uint64_t> lo{0};
+    ids.reserve(pieces.size());
+    for (std::string_view p : pieces) {
+      int32_t t = spmx_piece_to_id(h_, p.data(), p.size());
+      if (t == unk && p != unk_name && !to_unk) {
+        lit.append(p.data(), p.size());
+        lo.push_back(lit.size());
+        t = -static_cast<int32_t>(lo.size() - 1);
+      }
+      ids.push_back(t);
+    }
+    return DecodeSpans(ids.data(), ids.size(), &lit, &lo, spt);
+  }
+  virtual util::Status Decode(const std::vector<std::string> &pieces, SentencePieceText *spt) const {
+    std::vector<std::string_view> v(pieces.begin(), pieces.end());
+    return Decode(v, spt);
+  }
+  // sentencepiece_processor.h:553-569: the serialized SentencePieceText of the above; errors are swallowed
+  virtual std::string DecodeIdsAsSerializedProto(const std::vector<int> &ids) const {
+    SentencePieceText spt;
+    if (!Decode(ids, &spt).ok()) return std::string();
+    return spt.SerializeAsString();
+  }
+  virtual std::string DecodePiecesAsSerializedProto(const std::vector<std::string_view> &pieces) const {
+    SentencePieceText spt;
+    if (!Decode(pieces, &spt).ok()) return std::string();
+    return spt.SerializeAsString();
+  }
+  virtual std::string DecodePiecesAsSerializedProto(const std::vector<std::string> &pieces) const {
+    SentencePieceText spt;
+    if (!Decode(pieces, &spt).ok()) return std::string();
+    return spt.SerializeAsString();
+  }
   // EncodeAsSerializedProto (sentencepiece_processor.h:528-531): the serialized SentencePieceText of Encode(input, &spt)
   virtual std::string EncodeAsSerializedProto(std::string_view input) const {
     SentencePieceText spt;
@@ -799,6 +851,48 @@ class SentencePieceProcessor {
     }
   }
   int device_ = 0;
+  // One sentence through the spans form of the decode calls; lit / lit_offsets: the pieces outside the vocabulary (ids
+  // -(k + 1)), null for the ids form.
+  util::Status DecodeSpans(const int32_t *ids, size_t n_ids, const std::string *lit, const std::vector<uint64_t> *lit_offsets,
+                           SentencePieceText *spt) const {
+    spt->text.clear();
+    spt->pieces.clear();
+    spt->has_score = false;
+    char *text = nullptr, *raw = nullptr;
+    uint64_t *offs = nullptr, *poffs = nullptr, *roffs = nullptr;
+    int32_t *pid = nullptr;
+    uint32_t *begin = nullptr, *end = nullptr;
+    const uint64_t io[2] = {0, n_ids};
+    const int32_t none = 0;
+    if (n_ids == 0) ids = &none;
+    const int rc = lit ? spmx_decode_batch_pieces_spans(h_, ids, io, 1, lit->data(), lit_offsets->data(), lit_offsets->size() - 1, &text,
+                                                        &offs, &pid, &begin, &end, &poffs, &raw, &roffs)
+                       : spmx_decode_batch_spans(h_, ids, io, 1, &text, &offs, &pid, &begin, &end, &poffs, &raw, &roffs);
+    if (rc != 0) return FromHandle(rc);
+    spt->text.assign(text, text + offs[1]);
+    const char *surf = raw ? raw : text;      // the text the ranges index: before the denormalizer
+    const bool to_unk = spmx_decode_unk_option(h_) != 0;
+    const int unk = unk_id();
+    spt->pieces.resize(poffs[1]);
+    for (uint64_t k = 0; k < poffs[1]; ++k) {
+      SentencePieceText::SentencePiece &p = spt->pieces[k];
+      const int32_t t = pid[k];
+      if (t < 0) {
+        const uint64_t q = static_cast<uint64_t>(-(t + 1));
+        p.piece.assign(lit->data() + (*lit_offsets)[q], lit->data() + (*lit_offsets)[q + 1]);
+        p.id = static_cast<uint32_t>(unk);
+      } else {
+        p.piece = (to_unk && IsUnknown(t)) ? UnkPiece() : IdToPiece(t);      // .cc:1050-1058
+        p.id = static_cast<uint32_t>(t);
+      }
+      p.begin = begin[k];
+      p.end = end[k];
+      p.surface.assign(surf + begin[k], surf + end[k]);
+      p.has_surface = true;
+    }
+    spmx_free(text); spmx_free(offs); spmx_free(pid); spmx_free(begin); spmx_free(end); spmx_free(poffs); spmx_free(raw); spmx_free(roffs);
+    return util::Status();
+  }
   bool unk_piece_option_ = false;   // the `unk` / `unk_piece` extra option: piece strings only (:1050-1058)
   bool reverse_option_ = false;     // an odd number of `reverse` options: the pieces come out last first
   spmx_handle *h_ = nullptr;

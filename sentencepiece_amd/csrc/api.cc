@@ -234,6 +234,8 @@ struct Workspace {
   DevBuf<int32_t> d_ids;
   DevBuf<uint8_t> d_lit_bytes;           // Decode(pieces): the pieces outside the vocabulary (kernels_decode.h DecodeArgs::lit_*)
   DevBuf<uint32_t> d_lit_offs;
+  DevBuf<int32_t> d_dec_ids;             // spans form of the host decode calls: the piece ids in output order, the piece offsets
+  DevBuf<uint64_t> d_dec_poffs;
   const uint8_t *lit_bytes = nullptr;    // set for the duration of one spmx_decode_batch_pieces call
   const uint32_t *lit_offs = nullptr;
   uint32_t n_lit = 0;
@@ -1559,14 +1561,28 @@ int NormalizeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, const 
   return kOk;
 }
 
+// The device outputs of the spans form (kernels_decode.h DecodeArgs::span_*): `capacity` entries each, offs n + 1.
+struct DecodeSpanOut {
+  int32_t *ids;
+  uint32_t *begin, *end;
+  uint64_t *offs;
+  uint64_t capacity;
+  uint64_t total;      // out: pieces of the batch (valid whenever the ids were)
+};
+
 // Batch Decode on the device (kernels_decode.h): count pass -> scan -> (host checks status / capacity) -> write pass.
+// so: the spans form.  Its write pass runs whenever the piece outputs are large enough, also for a batch without text and
+// for a text that does not fit (the spans are then valid, the text is not).
 int DecodeRaw(spmx_handle *h, Workspace *ws, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, uint8_t *d_text,
-              uint64_t text_capacity, uint64_t *d_text_offsets, hipStream_t stream, uint64_t *total_bytes) {
+              uint64_t text_capacity, uint64_t *d_text_offsets, hipStream_t stream, uint64_t *total_bytes,
+              DecodeSpanOut *so = nullptr) {
   if (total_bytes) *total_bytes = 0;
+  if (so) so->total = 0;
   if (n >= (1ull << 32) - 64) return Fail(h, kInvalidArgument, "more than 2^32 - 64 sentences in one batch");
-  if (!d_id_offsets || !d_text_offsets) return Fail(h, kInvalidArgument, "null offsets");
+  if (!d_id_offsets || !d_text_offsets || (so && !so->offs)) return Fail(h, kInvalidArgument, "null offsets");
   if (n == 0) {
     HIP_OR_RETURN(h, hipMemsetAsync(d_text_offsets, 0, sizeof(uint64_t), stream));
+    if (so) HIP_OR_RETURN(h, hipMemsetAsync(so->offs, 0, sizeof(uint64_t), stream));
     HIP_OR_RETURN(h, hipStreamSynchronize(stream));
     return kOk;
   }
@@ -1594,6 +1610,11 @@ int DecodeRaw(spmx_handle *h, Workspace *ws, const int32_t *d_ids, const uint64_
   }
   HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_ctrl, ws->d_ctrl, offsetof(Ctrl, total_ids), hipMemcpyDeviceToHost, stream));
   HIP_OR_RETURN(h, hipMemcpyAsync(&ws->h_ctrl->total_ids, d_text_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  uint64_t id_range[2] = {0, 0};         // spans form: id_offsets[0], id_offsets[n]
+  if (so) {
+    HIP_OR_RETURN(h, hipMemcpyAsync(&id_range[0], d_id_offsets, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OR_RETURN(h, hipMemcpyAsync(&id_range[1], d_id_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  }
   HIP_OR_RETURN(h, hipStreamSynchronize(stream));
   if (ws->h_ctrl->status & kStBadId) {   // sentencepiece_processor.cc:913-917 (the id reported is one of the batch's first failing sentence)
     const int id = static_cast<int>(static_cast<uint32_t>(ws->h_ctrl->bad_key));
@@ -1601,6 +1622,18 @@ int DecodeRaw(spmx_handle *h, Workspace *ws, const int32_t *d_ids, const uint64_
   }
   const uint64_t total = ws->h_ctrl->total_ids;
   if (total_bytes) *total_bytes = total;
+  if (so) {
+    so->total = id_range[1] - id_range[0] + n * static_cast<uint64_t>(a.x_npre + a.x_nsuf);
+    const bool fits = so->total == 0 || (so->ids && so->begin && so->end && so->total <= so->capacity);
+    if (fits) {
+      a.span_begin = so->begin; a.span_end = so->end; a.piece_ids = so->ids; a.piece_offs = so->offs;   // (no pieces: only offs is written)
+      HIP_OR_RETURN(h, LaunchDecode(true, a, grid, stream));
+      HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+    }
+    if (total && (!d_text || total > text_capacity)) return Fail(h, kResourceExhausted, "text_capacity is too small");
+    if (!fits) return Fail(h, kResourceExhausted, "piece_capacity is too small");
+    return kOk;
+  }
   if (total == 0) return kOk;
   if (!d_text || total > text_capacity) return Fail(h, kResourceExhausted, "text_capacity is too small");
   HIP_OR_RETURN(h, LaunchDecode(true, a, grid, stream));
@@ -1610,10 +1643,18 @@ int DecodeRaw(spmx_handle *h, Workspace *ws, const int32_t *d_ids, const uint64_
 
 // Decode, then the denormalizer over each decoded sentence when the model carries one (`*text = denormalizer_->
 // Normalize(*text)`, sentencepiece_processor.cc:905-907): the batch Normalize kernels with the denormalizer's tables.
+// so (spans form): the spans index the text before the denormalizer, which stays in ws->d_dn_text / d_dn_offs, *raw_bytes long.
 int DecodeDevice(spmx_handle *h, Workspace *ws, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, uint8_t *d_text,
-                 uint64_t text_capacity, uint64_t *d_text_offsets, hipStream_t stream, uint64_t *total_bytes) {
-  if (!h->model.has_denormalizer)
-    return DecodeRaw(h, ws, d_ids, d_id_offsets, n, d_text, text_capacity, d_text_offsets, stream, total_bytes);
+                 uint64_t text_capacity, uint64_t *d_text_offsets, hipStream_t stream, uint64_t *total_bytes,
+                 DecodeSpanOut *so = nullptr, uint64_t *raw_bytes = nullptr) {
+  if (raw_bytes) *raw_bytes = 0;
+  if (!h->model.has_denormalizer) {
+    uint64_t total = 0;
+    const int rc = DecodeRaw(h, ws, d_ids, d_id_offsets, n, d_text, text_capacity, d_text_offsets, stream, &total, so);
+    if (total_bytes) *total_bytes = total;
+    if (raw_bytes) *raw_bytes = total;
+    return rc;
+  }
   if (total_bytes) *total_bytes = 0;
   if (!d_id_offsets || !d_text_offsets) return Fail(h, kInvalidArgument, "null offsets");
   HIP_OR_RETURN(h, ws->d_dn_offs.Reserve(n + 1));
@@ -1621,10 +1662,11 @@ int DecodeDevice(spmx_handle *h, Workspace *ws, const int32_t *d_ids, const uint
   int rc = kOk;
   for (int attempt = 0; attempt < 2; ++attempt) {
     HIP_OR_RETURN(h, ws->d_dn_text.Reserve(cap));
-    rc = DecodeRaw(h, ws, d_ids, d_id_offsets, n, ws->d_dn_text.p, ws->d_dn_text.cap, ws->d_dn_offs.p, stream, &total);
+    rc = DecodeRaw(h, ws, d_ids, d_id_offsets, n, ws->d_dn_text.p, ws->d_dn_text.cap, ws->d_dn_offs.p, stream, &total, so);
     if (rc != kResourceExhausted || total <= ws->d_dn_text.cap) break;
     cap = total + 64;
   }
+  if (raw_bytes) *raw_bytes = total;
   if (rc != kOk) return rc;
   rc = NormalizeDevice(h, ws, ws->d_dn_text.p, ws->d_dn_offs.p, n, d_text, d_text ? text_capacity : 0, d_text_offsets, nullptr, stream,
                        total_bytes, false, &h->dn_dev);
@@ -2880,9 +2922,66 @@ int spmx_decode_batch_device(spmx_handle *h, const int32_t *d_ids, const uint64_
   });
 }
 
+int spmx_decode_batch_spans_device(spmx_handle *h, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, void *d_text,
+                                   uint64_t text_capacity, uint64_t *d_text_offsets, int32_t *d_piece_ids, uint32_t *d_span_begin,
+                                   uint32_t *d_span_end, uint64_t piece_capacity, uint64_t *d_piece_offsets, void *d_raw_text,
+                                   uint64_t raw_capacity, uint64_t *d_raw_offsets, void *stream, uint64_t *total_bytes,
+                                   uint64_t *total_pieces, uint64_t *raw_bytes) {
+  if (!h) return kInvalidArgument;
+  if (total_pieces) *total_pieces = 0;
+  return Guard(h, [&]() -> int {
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    Workspace *ws = L.ws.get();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DecodeSpanOut so{d_piece_ids, d_span_begin, d_span_end, d_piece_offsets, piece_capacity, 0};
+    uint64_t raw = 0;
+    int rc = DecodeDevice(h, ws, d_ids, d_id_offsets, n, static_cast<uint8_t *>(d_text), text_capacity, d_text_offsets, st,
+                          total_bytes, &so, &raw);
+    if (total_pieces) *total_pieces = so.total;
+    if (raw_bytes) *raw_bytes = raw;
+    if (rc != kOk || !h->model.has_denormalizer) return rc;
+    // the text the spans index: a copy of what the denormalizer read
+    if (!d_raw_offsets || (raw && (!d_raw_text || raw > raw_capacity))) return Fail(h, kResourceExhausted, "raw_capacity is too small");
+    HIP_OR_RETURN(h, hipMemcpyAsync(d_raw_offsets, ws->d_dn_offs.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    if (raw) HIP_OR_RETURN(h, hipMemcpyAsync(d_raw_text, ws->d_dn_text.p, raw, hipMemcpyDeviceToDevice, st));
+    HIP_OR_RETURN(h, hipStreamSynchronize(st));
+    return kOk;
+  });
+}
+
 namespace {
+// The host-array outputs of the spans form (null: the plain form).
+struct DecodeSpanHost {
+  int32_t **piece_ids;
+  uint32_t **begin, **end;
+  uint64_t **piece_offsets;
+  char **raw_text;
+  uint64_t **raw_offsets;
+};
 int DecodeBatchHost(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, const char *lit_bytes,
-                    const uint64_t *lit_offsets, uint64_t n_lit, char **text, uint64_t **text_offsets);
+                    const uint64_t *lit_offsets, uint64_t n_lit, char **text, uint64_t **text_offsets,
+                    const DecodeSpanHost *sp = nullptr);
+bool SpanHostOk(const DecodeSpanHost &sp) {
+  return sp.piece_ids && sp.begin && sp.end && sp.piece_offsets && sp.raw_text && sp.raw_offsets;
+}
+}
+int spmx_decode_batch_spans(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, char **text,
+                            uint64_t **text_offsets, int32_t **piece_ids, uint32_t **span_begin, uint32_t **span_end,
+                            uint64_t **piece_offsets, char **raw_text, uint64_t **raw_offsets) {
+  const DecodeSpanHost sp{piece_ids, span_begin, span_end, piece_offsets, raw_text, raw_offsets};
+  if (h && !SpanHostOk(sp)) return Fail(h, kInternal, "output container is null");
+  return DecodeBatchHost(h, ids, id_offsets, n, nullptr, nullptr, 0, text, text_offsets, &sp);
+}
+int spmx_decode_batch_pieces_spans(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n,
+                                   const char *lit_bytes, const uint64_t *lit_offsets, uint64_t n_lit, char **text,
+                                   uint64_t **text_offsets, int32_t **piece_ids, uint32_t **span_begin, uint32_t **span_end,
+                                   uint64_t **piece_offsets, char **raw_text, uint64_t **raw_offsets) {
+  const DecodeSpanHost sp{piece_ids, span_begin, span_end, piece_offsets, raw_text, raw_offsets};
+  if (h && !SpanHostOk(sp)) return Fail(h, kInternal, "output container is null");
+  if (h && n_lit && (!lit_offsets || (lit_offsets[n_lit] && !lit_bytes))) return Fail(h, kInvalidArgument, "null literal pieces");
+  return DecodeBatchHost(h, ids, id_offsets, n, lit_bytes, lit_offsets, n_lit, text, text_offsets, &sp);
 }
 int spmx_decode_batch(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, char **text,
                       uint64_t **text_offsets) {
@@ -2898,6 +2997,7 @@ int spmx_piece_score(const spmx_handle *h, int id, float *score) {
   *score = h->model.pieces[static_cast<size_t>(id)].score;
   return kOk;
 }
+int spmx_has_denormalizer(const spmx_handle *h) { return h && h->model.has_denormalizer ? 1 : 0; }
 int spmx_decode_unk_option(const spmx_handle *h) { return h && h->dx_unk ? 1 : 0; }
 int spmx_serialized_model(const spmx_handle *h, const char **data, uint64_t *n_bytes) {
   if (!h || !data || !n_bytes) return kInvalidArgument;
@@ -2907,10 +3007,11 @@ int spmx_serialized_model(const spmx_handle *h, const char **data, uint64_t *n_b
 }
 namespace {
 int DecodeBatchHost(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, const char *lit_bytes,
-                    const uint64_t *lit_offsets, uint64_t n_lit, char **text, uint64_t **text_offsets) {
+                    const uint64_t *lit_offsets, uint64_t n_lit, char **text, uint64_t **text_offsets, const DecodeSpanHost *sp) {
   if (!h) return kInvalidArgument;
   if (!text || !text_offsets) return Fail(h, kInternal, "output container is null");
   *text = nullptr; *text_offsets = nullptr;
+  if (sp) { *sp->piece_ids = nullptr; *sp->begin = nullptr; *sp->end = nullptr; *sp->piece_offsets = nullptr; *sp->raw_text = nullptr; *sp->raw_offsets = nullptr; }
   if (n && !id_offsets) return Fail(h, kInvalidArgument, "null offsets");
   return Guard(h, [&]() -> int {
     HIP_OR_RETURN(h, hipSetDevice(h->device));
@@ -2920,7 +3021,11 @@ int DecodeBatchHost(spmx_handle *h, const int32_t *ids, const uint64_t *id_offse
     hipStream_t st = ws->stream;
     uint64_t *ho = static_cast<uint64_t *>(malloc((n + 1) * sizeof(uint64_t)));
     if (!ho) return Fail(h, kResourceExhausted, "out of host memory");
-    if (n == 0) { ho[0] = 0; *text_offsets = ho; *text = static_cast<char *>(malloc(1)); return kOk; }
+    if (n == 0) {
+      ho[0] = 0; *text_offsets = ho; *text = static_cast<char *>(malloc(1));
+      if (sp) { *sp->piece_offsets = static_cast<uint64_t *>(calloc(1, sizeof(uint64_t))); *sp->piece_ids = static_cast<int32_t *>(malloc(4)); *sp->begin = static_cast<uint32_t *>(malloc(4)); *sp->end = static_cast<uint32_t *>(malloc(4)); }
+      return kOk;
+    }
     const uint64_t base = id_offsets[0], n_ids = id_offsets[n] - base;
     hipError_t e = ws->d_ids.Reserve(n_ids + 16);
     if (e == hipSuccess) e = ws->d_offs.Reserve(n + 1);
@@ -2944,21 +3049,57 @@ int DecodeBatchHost(spmx_handle *h, const int32_t *ids, const uint64_t *id_offse
     }
     if (e != hipSuccess) { free(ho); return FailHip(h, e, "staging the ids"); }
     const int32_t *d_ids = ws->d_ids.p - base;     // the kernels address ids + id_offsets[i]
-    uint64_t cap = n_ids * 6 + 64, total = 0;
+    uint64_t cap = n_ids * 6 + 64, total = 0, raw = 0;
     int rc = kOk;
+    DecodeSpanOut so{};
+    if (sp) {      // at most kMaxExtra pieces of the extra options on either side of a sentence
+      so.capacity = n_ids + n * 2 * static_cast<uint64_t>(kMaxExtra) + 1;
+      hipError_t e3 = ws->d_dec_ids.Reserve(so.capacity);
+      if (e3 == hipSuccess) e3 = ws->d_span_begin.Reserve(so.capacity);
+      if (e3 == hipSuccess) e3 = ws->d_span_end.Reserve(so.capacity);
+      if (e3 == hipSuccess) e3 = ws->d_dec_poffs.Reserve(n + 1);
+      if (e3 != hipSuccess) { free(ho); return FailHip(h, e3, "hipMalloc(spans)"); }
+      so.ids = ws->d_dec_ids.p; so.begin = ws->d_span_begin.p; so.end = ws->d_span_end.p; so.offs = ws->d_dec_poffs.p;
+    }
     for (int attempt = 0; attempt < 2; ++attempt) {
       if (hipError_t e2 = ws->d_text.Reserve(cap); e2 != hipSuccess) { free(ho); return FailHip(h, e2, "hipMalloc(text)"); }
-      rc = DecodeDevice(h, ws, d_ids, ws->d_offs.p, n, ws->d_text.p, ws->d_text.cap, ws->d_id_offs.p, st, &total);
+      rc = DecodeDevice(h, ws, d_ids, ws->d_offs.p, n, ws->d_text.p, ws->d_text.cap, ws->d_id_offs.p, st, &total, sp ? &so : nullptr, &raw);
       if (rc != kResourceExhausted || total <= ws->d_text.cap) break;
       cap = total;
     }
     if (rc != kOk) { free(ho); return rc; }
+    if (sp) {
+      const uint64_t np = so.total;
+      int32_t *hi = static_cast<int32_t *>(malloc((np ? np : 1) * sizeof(int32_t)));
+      uint32_t *hb = static_cast<uint32_t *>(malloc((np ? np : 1) * sizeof(uint32_t)));
+      uint32_t *he = static_cast<uint32_t *>(malloc((np ? np : 1) * sizeof(uint32_t)));
+      uint64_t *hp = static_cast<uint64_t *>(malloc((n + 1) * sizeof(uint64_t)));
+      const bool dn = h->model.has_denormalizer;
+      char *hr = dn ? static_cast<char *>(malloc(raw ? raw : 1)) : nullptr;
+      uint64_t *hro = dn ? static_cast<uint64_t *>(malloc((n + 1) * sizeof(uint64_t))) : nullptr;
+      hipError_t e4 = (!hi || !hb || !he || !hp || (dn && (!hr || !hro))) ? hipErrorOutOfMemory : hipSuccess;
+      if (e4 == hipSuccess) e4 = hipMemcpyAsync(hp, so.offs, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+      if (e4 == hipSuccess && np) e4 = hipMemcpyAsync(hi, so.ids, np * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+      if (e4 == hipSuccess && np) e4 = hipMemcpyAsync(hb, so.begin, np * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+      if (e4 == hipSuccess && np) e4 = hipMemcpyAsync(he, so.end, np * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+      if (e4 == hipSuccess && dn) e4 = hipMemcpyAsync(hro, ws->d_dn_offs.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+      if (e4 == hipSuccess && dn && raw) e4 = hipMemcpyAsync(hr, ws->d_dn_text.p, raw, hipMemcpyDeviceToHost, st);
+      if (e4 == hipSuccess) e4 = hipStreamSynchronize(st);
+      if (e4 != hipSuccess) { free(ho); free(hi); free(hb); free(he); free(hp); free(hr); free(hro); return FailHip(h, e4, "hipMemcpy(spans)"); }
+      *sp->piece_ids = hi; *sp->begin = hb; *sp->end = he; *sp->piece_offsets = hp; *sp->raw_text = hr; *sp->raw_offsets = hro;
+    }
+    auto drop_spans = [&]() {
+      if (!sp) return;
+      void **out[6] = {reinterpret_cast<void **>(sp->piece_ids), reinterpret_cast<void **>(sp->begin), reinterpret_cast<void **>(sp->end),
+                       reinterpret_cast<void **>(sp->piece_offsets), reinterpret_cast<void **>(sp->raw_text), reinterpret_cast<void **>(sp->raw_offsets)};
+      for (void **o : out) { free(*o); *o = nullptr; }
+    };
     char *ht = static_cast<char *>(malloc(total ? total : 1));
-    if (!ht) { free(ho); return Fail(h, kResourceExhausted, "out of host memory"); }
+    if (!ht) { free(ho); drop_spans(); return Fail(h, kResourceExhausted, "out of host memory"); }
     e = hipMemcpyAsync(ho, ws->d_id_offs.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && total) e = hipMemcpyAsync(ht, ws->d_text.p, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { free(ho); free(ht); return FailHip(h, e, "hipMemcpy(text)"); }
+    if (e != hipSuccess) { free(ho); free(ht); drop_spans(); return FailHip(h, e, "hipMemcpy(text)"); }
     *text = ht;
     *text_offsets = ho;
     return kOk;

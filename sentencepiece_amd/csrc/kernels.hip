@@ -126,8 +126,9 @@ __global__ __launch_bounds__(64) void SplitWriteKernel(SplitArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kSplitLdsBytes];
   split_block<true>(a, stage);
 }
-__global__ __launch_bounds__(64) void DecodeCountKernel(DecodeArgs a) { decode_block<false>(a); }
-__global__ __launch_bounds__(64) void DecodeWriteKernel(DecodeArgs a) { decode_block<true>(a); }
+__global__ __launch_bounds__(64) void DecodeCountKernel(DecodeArgs a) { decode_body<false, false>(a); }
+__global__ __launch_bounds__(64) void DecodeWriteKernel(DecodeArgs a) { decode_body<true, false>(a); }
+__global__ __launch_bounds__(64) void DecodeWriteSpansKernel(DecodeArgs a) { decode_body<true, true>(a); }
 __global__ __launch_bounds__(256) void PlainScanKernel(PlainScanArgs a) { plain_scan_block<false>(a); }
 __global__ __launch_bounds__(256) void PlainScanKeepWsKernel(PlainScanArgs a) { plain_scan_block<true>(a); }
 __global__ __launch_bounds__(64) void ClassifyCountKernel(ClassifyArgs a) {
@@ -284,7 +285,8 @@ hipError_t LaunchSplit(bool write, const SplitArgs &a, int grid, hipStream_t str
 }
 
 hipError_t LaunchDecode(bool write, const DecodeArgs &a, int grid, hipStream_t stream) {
-  if (write) hipLaunchKernelGGL(DecodeWriteKernel, dim3(grid), dim3(64), 0, stream, a);
+  if (write && a.piece_offs != nullptr) hipLaunchKernelGGL(DecodeWriteSpansKernel, dim3(grid), dim3(64), 0, stream, a);
+  else if (write) hipLaunchKernelGGL(DecodeWriteKernel, dim3(grid), dim3(64), 0, stream, a);
   else hipLaunchKernelGGL(DecodeCountKernel, dim3(grid), dim3(64), 0, stream, a);
   return hipGetLastError();
 }

@@ -18,6 +18,10 @@
 //                         (kernels.h) over "byte pieces step by their character length, other pieces by 1";
 //                         a character that would straddle the end of the sweep opens the next sweep instead.
 // The kernel runs twice per call (count, then write) with a scan of the per-sentence lengths in between.
+// The spans form of the write pass (decode_body<true, true>; Decode(..., SentencePieceText*), :813-903) keeps what the sweep
+// computes anyway -- the lengths, their scan, the running offset, the starts S -- and writes per piece the byte range SetSurface
+// (:822-828) gives it: a start's own range, and for the later byte pieces of a character the range end of the start that owns
+// them (the highest bit of S at or below the lane: one shuffle), empty except on the character's last piece (:863-874).
 #ifndef SPMX_KERNELS_DECODE_H_
 #define SPMX_KERNELS_DECODE_H_
 
@@ -56,20 +60,40 @@ struct DecodeArgs {
   const uint8_t *lit_bytes;
   const uint32_t *lit_offs;
   uint32_t n_lit;
+  // Spans form (Decode(..., SentencePieceText*), :813-903), all null in the plain form: for position p of sentence s in the
+  // order after the extra options (n_body + x_npre + x_nsuf positions) the entry piece_base(s) + p holds what SetSurface
+  // (:822-828) sets -- the byte range [span_begin, span_end) of the piece's surface in the sentence's own text BEFORE the
+  // denormalizer -- and the id (a literal keeps its code -(k + 1)).  piece_base(s) = id_offs[s] - id_offs[0] +
+  // s * (x_npre + x_nsuf), also written to piece_offs[s] (n + 1 entries).  Of a character of k byte pieces at offset o the
+  // first k - 1 get (o, o), the last (o, o + k) (:863-874); an invalid byte piece (o, o + 3) (:857-861).
+  uint32_t *span_begin, *span_end;
+  int32_t *piece_ids;
+  uint64_t *piece_offs;
 };
 
-template <bool WRITE>
-SPMX_DEVICE void decode_block(const DecodeArgs &a) {
+// SPANS (with WRITE): the spans form above; the text is written only if it fits, the spans always (the host has checked
+// their capacity).
+template <bool WRITE, bool SPANS>
+SPMX_DEVICE void decode_body(const DecodeArgs &a) {
   const int lane = wv::lane();
   const SpmxDev &d = a.dev;
   const bool rm = (d.flags & kNfRemoveExtraWs) != 0;
   const bool strip = rm || (d.flags & kNfAddDummyPrefix) != 0;
-  if (WRITE && a.text_offs[a.n] > a.text_cap) return;      // caller sees the needed size in text_offs[n]
+  const bool text_ok = !WRITE || a.text_offs[a.n] <= a.text_cap;
+  if (WRITE && !SPANS && !text_ok) return;      // caller sees the needed size in text_offs[n]
   for (uint32_t s = static_cast<uint32_t>(wv::block_id()); s < a.n; s += static_cast<uint32_t>(wv::grid_size())) {
     const uint64_t beg = a.id_offs[s];
     const int n_body = static_cast<int>(a.id_offs[s + 1] - beg);
     const int n_pieces = n_body + a.x_npre + a.x_nsuf;
     uint8_t *dst = WRITE ? a.text + a.text_offs[s] : nullptr;
+    uint64_t pbase = 0;
+    if (SPANS) {
+      pbase = beg - a.id_offs[0] + static_cast<uint64_t>(s) * static_cast<uint64_t>(a.x_npre + a.x_nsuf);
+      if (lane == 0) {
+        a.piece_offs[s] = pbase;
+        if (s + 1 == a.n) a.piece_offs[a.n] = pbase + static_cast<uint64_t>(n_pieces);
+      }
+    }
     uint32_t out = 0;            // bytes of this sentence so far
     bool bos = true;             // is_bos_ws
     bool bad = false;
@@ -162,7 +186,24 @@ SPMX_DEVICE void decode_block(const DecodeArgs &a) {
       }
       int total = 0;
       const uint32_t rel = static_cast<uint32_t>(wave_excl_scan(static_cast<int>(olen), lane, &total));
-      if (WRITE && total > 0) {
+      if (SPANS) {
+        // every piece below proc_end belongs to the unit of the last start at or below it: a piece that is no start is a
+        // later byte piece of a character, whose range is empty unless it is the character's last
+        const uint64_t at_or_below = S & (~0ull >> (63 - lane));
+        const int own = at_or_below ? 63 - wv::clz64(at_or_below) : lane;
+        const uint32_t po = wv::shfl(rel | (static_cast<uint32_t>(step) << 24), own);   // rel < 64 * 65536
+        const uint32_t o = out + (po & 0xFFFFFFu), k = po >> 24;
+        uint32_t e = o;
+        if (own == lane) { if (!(is_byte && k > 1u)) e = o + olen; }
+        else if (lane == own + static_cast<int>(k) - 1) e = o + k;
+        if (valid && i < proc_end) {
+          const uint64_t at = pbase + static_cast<uint64_t>(i);
+          a.span_begin[at] = o;
+          a.span_end[at] = e;
+          a.piece_ids[at] = id;
+        }
+      }
+      if (WRITE && total > 0 && (!SPANS || text_ok)) {
         // every output byte of the sweep finds its piece: the last lane whose offset is <= j (lanes without
         // output share the offset of the next one and lose to it).  All cross-lane reads sit in uniform flow.
         const uint32_t src = off + skip;
@@ -194,6 +235,13 @@ SPMX_DEVICE void decode_block(const DecodeArgs &a) {
     if (wv::any(bad)) { if (lane == 0) wv::atomic_or(a.status, kStBadId); out = 0; }   // the host stops before the write pass
     if (!WRITE && lane == 0) a.counts[s] = out;
   }
+}
+
+// The entry of the write pass for a launcher that knows two passes only: the spans form when its outputs are set.
+template <bool WRITE>
+SPMX_DEVICE void decode_block(const DecodeArgs &a) {
+  if (WRITE && a.piece_offs != nullptr) decode_body<true, true>(a);
+  else decode_body<WRITE, false>(a);
 }
 
 }  // namespace spmx

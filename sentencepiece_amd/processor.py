@@ -34,6 +34,7 @@ def _pyext():
 
 _OK = 0
 _RESOURCE_EXHAUSTED = 8
+_PROTO_TYPES = ("serialized_proto", "proto", "immutable_proto")     # the SentencePieceText forms of out_type
 
 
 class SentencePieceProcessor:
@@ -902,7 +903,8 @@ class SentencePieceProcessor:
         """``DecodePieces`` (:871-872, ``_DecodePiecesBatch`` sentencepiece.i:547): pieces -> text.  A piece that is not in
         the vocabulary is copied through as text (src/sentencepiece_processor.cc:784-790): it travels to the decode
         kernels as a literal beside the ids (``spmx_decode_batch_pieces``); under a decode extra option ``unk`` the
-        reference rewrites it to the unknown piece first (.cc:1050-1058)."""
+        reference rewrites it to the unknown piece first (.cc:1050-1058).  ``out_type="serialized_proto"`` /
+        ``"immutable_proto"``: the ``SentencePieceText`` form, see ``DecodeIdsAsSerializedProto``."""
         self._need()
         single = not input or isinstance(input[0], (str, bytes))
         items = [input] if single else input
@@ -925,6 +927,9 @@ class SentencePieceProcessor:
         if lits:
             np.cumsum([len(x) for x in lits], out=lo[1:])
         blob = b"".join(lits)
+        if out_type in _PROTO_TYPES:
+            res = self._decode_protos(self._decode_spans_host(ids, offs, blob, lo, len(lits)), lits, out_type)
+            return res[0] if single else res
         p_text, p_off = C.c_void_p(), C.c_void_p()
         self._check(self._lib.spmx_decode_batch_pieces(self._h, ids.ctypes.data if len(ids) else None, offs.ctypes.data, len(items),
                                                        blob if blob else None, lo.ctypes.data, len(lits), C.byref(p_text), C.byref(p_off)))
@@ -1007,7 +1012,8 @@ class SentencePieceProcessor:
     # ----------------------------------------------------------- decode ----
     def Decode(self, input, out_type=str, num_threads=None):
         """list[int] -> str; list[list[int]] -> list[str] (``Decode`` / ``_DecodeIdsBatch``,
-        python/src/sentencepiece/__init__.py:808-870).  ``out_type=bytes`` returns the raw bytes."""
+        python/src/sentencepiece/__init__.py:808-870).  ``out_type=bytes`` returns the raw bytes,
+        ``"serialized_proto"`` / ``"immutable_proto"`` the ``SentencePieceText`` form (``DecodeIdsAsSerializedProto``)."""
         self._need()
         single = not input or isinstance(input[0], (int, np.integer))
         items = [input] if single else input
@@ -1015,6 +1021,9 @@ class SentencePieceProcessor:
         if items:
             np.cumsum([len(x) for x in items], out=offs[1:])
         ids = np.fromiter((t for x in items for t in x), dtype=np.int32, count=int(offs[-1]))
+        if out_type in _PROTO_TYPES:
+            res = self._decode_protos(self._decode_spans_host(ids, offs, b"", None, 0), [], out_type)
+            return res[0] if single else res
         text, to = self.DecodePacked(ids, offs)
         b = text.tobytes()
         to = to.astype(np.int64)
@@ -1043,6 +1052,143 @@ class SentencePieceProcessor:
             self._lib.spmx_free(p_text)
             self._lib.spmx_free(p_off)
         return text, to
+
+    # ---- Decode to SentencePieceText (src/sentencepiece_processor.cc:766-925) ----
+    def _decode_spans_host(self, ids, id_offsets, lit_blob, lit_offs, n_lit):
+        """The host-array spans calls -> ``(text, text_offsets, piece_ids, begin, end, piece_offsets, raw_text,
+        raw_offsets)`` as numpy arrays; without a denormalizer the raw pair is the text pair itself."""
+        self._need()
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        id_offsets = np.ascontiguousarray(id_offsets, dtype=np.uint64)
+        n = len(id_offsets) - 1
+        ps = [C.c_void_p() for _ in range(8)]
+        ip = ids.ctypes.data if len(ids) else None
+        refs = [C.byref(p) for p in ps]
+        if lit_offs is None:
+            self._check(self._lib.spmx_decode_batch_spans(self._h, ip, id_offsets.ctypes.data, n, *refs))
+        else:
+            self._check(self._lib.spmx_decode_batch_pieces_spans(self._h, ip, id_offsets.ctypes.data, n, lit_blob if lit_blob else None,
+                                                                 lit_offs.ctypes.data, n_lit, *refs))
+
+        def arr(p, ctype, dtype, count):
+            if not count or not p:
+                return np.zeros(0, dtype=dtype)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(count,)).copy()
+        try:
+            to = arr(ps[1], C.c_uint64, np.uint64, n + 1)
+            po = arr(ps[5], C.c_uint64, np.uint64, n + 1)
+            text = arr(ps[0], C.c_uint8, np.uint8, int(to[n]))
+            npc = int(po[n])
+            pid, b, e = arr(ps[2], C.c_int32, np.int32, npc), arr(ps[3], C.c_uint32, np.uint32, npc), arr(ps[4], C.c_uint32, np.uint32, npc)
+            if ps[7]:
+                ro = arr(ps[7], C.c_uint64, np.uint64, n + 1)
+                raw = arr(ps[6], C.c_uint8, np.uint8, int(ro[n]))
+            else:
+                raw, ro = text, to
+        finally:
+            for p in ps:
+                self._lib.spmx_free(p)
+        return text, to, pid, b, e, po, raw, ro
+
+    def DecodeSpansPacked(self, ids, id_offsets):
+        """CSR host arrays -> ``(text uint8, text_offsets uint64[n + 1], piece_ids int32, begin uint32, end uint32,
+        piece_offsets uint64[n + 1], raw_text uint8, raw_offsets uint64[n + 1])``: what ``Decode(ids, SentencePieceText*)``
+        fills, as arrays.  The pieces of sentence s are ``[piece_offsets[s], piece_offsets[s + 1])`` in the order after
+        ``SetDecodeExtraOptions``; ``begin`` / ``end`` are byte offsets into the sentence's own ``raw_text`` -- the text
+        before the denormalizer, which is ``text`` itself for a model without one."""
+        return self._decode_spans_host(ids, id_offsets, b"", None, 0)
+
+    def DecodeSpansDevice(self, d_ids, d_id_offsets, stream=None, out=None):
+        """Device-resident form over torch tensors (``d_ids`` int32, ``d_id_offsets`` int64[n + 1]) -> a dict of
+        tensors ``text, text_offsets, piece_ids, begin, end, piece_offsets, raw_text, raw_offsets`` (begin / end uint32
+        bit patterns in int32 tensors) and ``total_bytes, total_pieces, raw_bytes``; the raw pair is the text pair for a
+        model without a denormalizer.  ``out``: the dict of an earlier call over a batch of the same size, whose tensors
+        are written again instead of new ones."""
+        import torch
+        self._need()
+        dev = d_ids.device
+        n = d_id_offsets.numel() - 1
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        dn = bool(self._lib.spmx_has_denormalizer(self._h))
+        text_cap, piece_cap, raw_cap = d_ids.numel() * 6 + 64, d_ids.numel() + 1, (d_ids.numel() * 6 + 64 if dn else 0)
+        reuse = out is not None and out["text_offsets"].numel() == n + 1
+        d_to = out["text_offsets"] if reuse else torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_po = out["piece_offsets"] if reuse else torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_ro = (out["raw_offsets"] if reuse else torch.empty(n + 1, dtype=torch.int64, device=dev)) if dn else None
+        if reuse:
+            text_cap, piece_cap, raw_cap = out["text"].numel(), out["piece_ids"].numel(), (out["raw_text"].numel() if dn else 0)
+        tb, tp, rb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        for attempt in range(4):
+            if reuse and attempt == 0:
+                d_text, d_pid, d_b, d_e, d_raw = out["text"], out["piece_ids"], out["begin"], out["end"], (out["raw_text"] if dn else None)
+            else:
+                d_text = torch.empty(text_cap, dtype=torch.uint8, device=dev)
+                d_pid, d_b, d_e = (torch.empty(piece_cap, dtype=torch.int32, device=dev) for _ in range(3))
+                d_raw = torch.empty(raw_cap, dtype=torch.uint8, device=dev) if dn else None
+            rc = self._lib.spmx_decode_batch_spans_device(
+                self._h, d_ids.data_ptr(), d_id_offsets.data_ptr(), n, d_text.data_ptr(), text_cap, d_to.data_ptr(),
+                d_pid.data_ptr(), d_b.data_ptr(), d_e.data_ptr(), piece_cap, d_po.data_ptr(),
+                d_raw.data_ptr() if dn else None, raw_cap, d_ro.data_ptr() if dn else None, stream,
+                C.byref(tb), C.byref(tp), C.byref(rb))
+            grow = (tb.value > text_cap, tp.value > piece_cap, dn and rb.value > raw_cap)
+            if rc != _RESOURCE_EXHAUSTED or not any(grow):
+                break
+            text_cap, piece_cap, raw_cap = max(text_cap, tb.value), max(piece_cap, tp.value), max(raw_cap, rb.value)
+        self._check(rc)
+        return dict(text=d_text, text_offsets=d_to, piece_ids=d_pid, begin=d_b, end=d_e, piece_offsets=d_po,
+                    raw_text=d_raw if dn else d_text, raw_offsets=d_ro if dn else d_to,
+                    total_bytes=tb.value, total_pieces=tp.value, raw_bytes=rb.value)
+
+    def _decode_protos(self, arrays, lits, out_type):
+        """The arrays of ``_decode_spans_host`` -> per sentence the serialized ``SentencePieceText`` (or its read-only
+        view).  Every piece carries surface, begin and end (SetSurface, .cc:822-828); a literal ``-(k + 1)`` is ``lits[k]``
+        with the unknown id; under the decode extra option ``unk`` unknown pieces are renamed (.cc:1050-1058)."""
+        from . import spt_proto
+        text, to, pid, b, e, po, raw, ro = arrays
+        tb, rawb = text.tobytes(), raw.tobytes()
+        unk = self.unk_id()
+        unk_name = self.unk_piece().encode("utf-8") if self._lib.spmx_decode_unk_option(self._h) else None
+        names = {}
+        out = []
+        for s in range(len(to) - 1):
+            base = int(ro[s])
+            rows = []
+            for k in range(int(po[s]), int(po[s + 1])):
+                t = int(pid[k])
+                if t < 0:
+                    piece, t = lits[-t - 1], unk
+                else:
+                    piece = names.get(t)
+                    if piece is None:
+                        piece = names[t] = unk_name if unk_name is not None and self.IsUnknown(t) else self.IdToPiece(t).encode("utf-8")
+                rows.append((piece, t, rawb[base + int(b[k]):base + int(e[k])], int(b[k]), int(e[k])))
+            st = tb[int(to[s]):int(to[s + 1])]
+            blob = spt_proto.serialize(st, rows)
+            out.append(blob if out_type != "immutable_proto" else spt_proto.ImmutableSentencePieceText(st, rows, blob))
+        return out
+
+    def DecodeIdsAsSerializedProto(self, input):
+        """``DecodeIdsAsSerializedProto`` (src/sentencepiece_processor.h) / ``decode(out_type="serialized_proto")``: the
+        serialized ``SentencePieceText`` of ``Decode(ids, &spt)`` -- the text and, per piece, its string, id, surface and
+        the byte range of the surface in the text before the denormalizer.  A list of rows gives a list."""
+        return self.Decode(input, out_type="serialized_proto")
+
+    def DecodePiecesAsSerializedProto(self, input):
+        return self.DecodePieces(input, out_type="serialized_proto")
+
+    def DecodeIdsAsImmutableProto(self, input):
+        """``decode(out_type="immutable_proto")``: the read-only view, begin / end in characters as the reference's Python
+        wrapper converts them (``ConvertToUnicodeSpans``)."""
+        return self.Decode(input, out_type="immutable_proto")
+
+    def DecodePiecesAsImmutableProto(self, input):
+        return self.DecodePieces(input, out_type="immutable_proto")
+
+    decode_ids_as_serialized_proto = DecodeIdsAsSerializedProto
+    decode_pieces_as_serialized_proto = DecodePiecesAsSerializedProto
+    decode_ids_as_immutable_proto = DecodeIdsAsImmutableProto
+    decode_pieces_as_immutable_proto = DecodePiecesAsImmutableProto
 
     def DecodeDevice(self, d_ids, d_id_offsets, d_text=None, d_text_offsets=None, stream=None):
         """Device-resident form over torch tensors: ``d_ids`` int32, ``d_id_offsets`` int64[n + 1] ->
