@@ -13,8 +13,8 @@
  * Thread safety: like SentencePieceProcessor's const methods, a loaded handle
  * may be used for encoding / decoding from several host threads at once: every
  * call leases its own workspace and stream, so the calls overlap on the GPU.
- * The mutators (set_encode_extra_options, set_vocabulary, ...) must not race
- * with them, as in the reference.  spmx_last_error() is per calling thread.
+ * The mutators (set_encode_extra_options, set_vocabulary,
+ * override_normalizer_spec, ...) must not race with them, as in the reference.  spmx_last_error() is per calling thread.
  */
 #ifndef SPMX_H_
 #define SPMX_H_
@@ -51,6 +51,34 @@ int spmx_set_decode_extra_options(spmx_handle *h, const char *options);
 /* SetVocabulary / ResetVocabulary (src/sentencepiece_processor.h:279-283). */
 int spmx_set_vocabulary(spmx_handle *h, const char *const *pieces, const uint64_t *piece_lens, uint64_t n);
 int spmx_reset_vocabulary(spmx_handle *h);
+/* SentencePieceTrainer::SetProtoField(name, value, NormalizerSpec*) (src/spec_parser.h:256-270) applied to
+ * mutable_normalizer_spec() (src/sentencepiece_processor.h:699), n pairs in the given order: what the Python wrapper's
+ * OverrideNormalizerSpec(**kwargs) does (python/src/sentencepiece/sentencepiece.i:706-716, :1213-1217).
+ *   fields    add_dummy_prefix, remove_extra_whitespaces, escape_whitespaces: booleans as string_util::lexical_cast<bool>
+ *             reads them (src/util.h:60-77): 1 t true y yes / 0 f false n no, in any letter case; an empty value is true.
+ *             name, normalization_rule_tsv: kept in the ModelProto only; they do not change what is encoded, as in the
+ *             reference.  precompiled_charsmap: bytes (value_lens counts; a NULL value_lens means C strings throughout).
+ *             The reference leaves its normalizer reading a freed string after this edit (src/normalizer.cc:47-68), so
+ *             there is nothing to be equal to; here the invariant below defines it.
+ *   errors    an unknown field: NOT_FOUND (5) `unknown field name "X" in NormalizerSpec.`; an unparsable boolean:
+ *             INVALID_ARGUMENT (3) `cannot parse "V" as bool.`  The pairs before the failing one are applied, as the
+ *             reference's loop leaves them; that pair and the ones behind it are not.  A charsmap that spmx_create would
+ *             refuse gives spmx_create's error and changes nothing.
+ * INVARIANT: after any sequence of calls the handle behaves like one newly created from its own spmx_serialized_model()
+ * bytes -- the ModelProto it was loaded from with only the overridden normalizer_spec fields changed (an overridden
+ * field is written explicitly, also at its default, as set_x() leaves the has-bit; every other byte is kept) -- under the
+ * same SetVocabulary restriction, encode and decode extra options and profiling switch, all of which stay.  The self-test
+ * samples are not run again (nor does the reference run them).
+ * One call compiles and uploads the model's tables ONCE, however many pairs it carries -- what spmx_create costs without
+ * the parse and the self-test -- and not at all when every field keeps its value.  The new tables are built beside the
+ * old ones: if that fails (host or device memory, a bad charsmap) the handle keeps working on its previous spec.
+ * spmx_handle_info reports the new table bytes.
+ * Threading: as spmx_set_vocabulary.  It must not run while another call on the handle is in flight; before and after
+ * such calls it is safe, from any thread. */
+int spmx_override_normalizer_spec(spmx_handle *h, const char *const *fields, const char *const *values,
+                                  const uint64_t *value_lens, uint64_t n);
+/* model_proto().normalizer_spec()'s three switches as the handle applies them now (any pointer may be NULL). */
+int spmx_normalizer_spec(const spmx_handle *h, int *add_dummy_prefix, int *remove_extra_whitespaces, int *escape_whitespaces);
 
 /* ---- vocabulary accessors (src/sentencepiece_processor.h:638-677) -------- */
 int spmx_piece_size(const spmx_handle *h);                                  /* GetPieceSize */
@@ -256,7 +284,8 @@ int spmx_decode_batch_pieces(spmx_handle *h, const int32_t *ids, const uint64_t 
 int spmx_decode_unk_option(const spmx_handle *h);
 /* GetScore(id) (src/sentencepiece_processor.h:650): the piece's score as the ModelProto holds it; 11 for an id out of range. */
 int spmx_piece_score(const spmx_handle *h, int id, float *score);
-/* serialized_model_proto() (src/sentencepiece_processor.h:694): the bytes the handle was created from; owned by the handle. */
+/* serialized_model_proto() (src/sentencepiece_processor.h:694): the bytes the handle was created from, with the overrides of
+ * spmx_override_normalizer_spec patched in; owned by the handle, valid until the next override or spmx_destroy. */
 int spmx_serialized_model(const spmx_handle *h, const char **data, uint64_t *n_bytes);
 /* Host-buffer form; *text (total bytes) and *text_offsets (n + 1) are released with spmx_free(). */
 int spmx_decode_batch(spmx_handle *h, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, char **text,

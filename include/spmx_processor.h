@@ -22,6 +22,7 @@
 #include <random>
 #include <string>
 #include <string_view>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -135,6 +136,44 @@ class EncodedBatch {
   int32_t *ids_ = nullptr;
   uint64_t *offs_ = nullptr;
   uint64_t n_ = 0;
+};
+
+// What mutable_normalizer_spec() hands out (src/sentencepiece_processor.h:699): the NormalizerSpec accessors a caller of
+// the reference uses on that pointer (builtin_pb/sentencepiece_model.pb.h), over a loaded processor's handle.  Every
+// setter takes effect at once -- one spmx_override_normalizer_spec call, i.e. one rebuild of the device tables when the
+// value changes; a caller that flips several switches pays once with OverrideNormalizerSpec below.  Owned by the
+// processor and valid as long as it is: it looks the handle up at every call, so it follows a second Load() (and does
+// nothing while no model is loaded); like the mutators of the processor itself, not to be used while an Encode / Decode is in flight.
+class NormalizerSpec {
+ public:
+  bool add_dummy_prefix() const { return Get(0); }
+  bool remove_extra_whitespaces() const { return Get(1); }
+  bool escape_whitespaces() const { return Get(2); }
+  void set_add_dummy_prefix(bool v) { Set("add_dummy_prefix", v ? "1" : "0"); }
+  void set_remove_extra_whitespaces(bool v) { Set("remove_extra_whitespaces", v ? "1" : "0"); }
+  void set_escape_whitespaces(bool v) { Set("escape_whitespaces", v ? "1" : "0"); }
+  // kept in the ModelProto only (serialized_model_proto()): they change nothing that is encoded, as in the reference
+  void set_name(const std::string &v) { Set("name", v); }
+  void set_normalization_rule_tsv(const std::string &v) { Set("normalization_rule_tsv", v); }
+  // the Status of the last setter (a setter of the reference cannot fail; here a rebuild can run out of memory, and the
+  // handle then keeps its previous spec)
+  int last_code() const { return last_code_; }
+
+ private:
+  friend class SentencePieceProcessor;
+  bool Get(int which) const {
+    int v[3] = {1, 1, 1};
+    if (hp_ && *hp_) spmx_normalizer_spec(*hp_, &v[0], &v[1], &v[2]);
+    return v[which] != 0;
+  }
+  void Set(const char *field, const std::string &value) {
+    if (!hp_ || !*hp_) return;
+    const char *v = value.c_str();
+    const uint64_t n = value.size();
+    last_code_ = spmx_override_normalizer_spec(*hp_, &field, &v, &n, 1);
+  }
+  spmx_handle *const *hp_ = nullptr;   // the owning processor's handle slot: a pointer kept across a second Load() follows it
+  int last_code_ = 0;
 };
 
 class SentencePieceProcessor {
@@ -783,7 +822,26 @@ class SentencePieceProcessor {
     if (!h_ || spmx_piece_score(h_, id, &s) != 0) return 0.f;
     return s;
   }
-  // serialized_model_proto (sentencepiece_processor.h:694): the bytes the model was loaded from
+  // mutable_normalizer_spec (sentencepiece_processor.h:699, .cc:1120): null before a model is loaded, as the reference's
+  NormalizerSpec *mutable_normalizer_spec() const {
+    if (!h_) return nullptr;
+    spec_.hp_ = &h_;
+    return &spec_;
+  }
+  // The string form -- the Python wrapper's OverrideNormalizerSpec(**kwargs) (python/src/sentencepiece/sentencepiece.i:
+  // 706-716): SentencePieceTrainer::SetProtoField(name, value, mutable_normalizer_spec()) for every pair, in ONE call:
+  // one rebuild.  NOT_FOUND for an unknown field, INVALID_ARGUMENT for an unparsable boolean.  The pairs go in the map's
+  // iteration order, which is unspecified (the reference's wrapper takes the same container): the pairs before a
+  // failing one stay applied, but WHICH pairs came before it is not predictable -- after an error read the switches back.
+  util::Status OverrideNormalizerSpec(const std::unordered_map<std::string, std::string> &args) {
+    if (!h_) return status();
+    std::vector<const char *> f, v;
+    std::vector<uint64_t> l;
+    for (const auto &kv : args) { f.push_back(kv.first.c_str()); v.push_back(kv.second.c_str()); l.push_back(kv.second.size()); }
+    return FromHandle(spmx_override_normalizer_spec(h_, f.data(), v.data(), l.data(), f.size()));
+  }
+  // serialized_model_proto (sentencepiece_processor.h:694): the bytes the model was loaded from, with the normalizer_spec
+  // edits made since patched in
   std::string serialized_model_proto() const {
     const char *p = nullptr;
     uint64_t n = 0;
@@ -896,6 +954,7 @@ class SentencePieceProcessor {
   bool unk_piece_option_ = false;   // the `unk` / `unk_piece` extra option: piece strings only (:1050-1058)
   bool reverse_option_ = false;     // an odd number of `reverse` options: the pieces come out last first
   spmx_handle *h_ = nullptr;
+  mutable NormalizerSpec spec_;       // what mutable_normalizer_spec() returns
 };
 
 }  // namespace sentencepiece_amd

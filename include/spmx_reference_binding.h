@@ -7,9 +7,12 @@
 // base-class pointer with spm_encode's loop (src/spm_encode_main.cc:115-119).
 #ifndef SPMX_REFERENCE_BINDING_H_
 #define SPMX_REFERENCE_BINDING_H_
+#include <atomic>
+#include <mutex>
 #include <string>
 #include <vector>
 
+#include "sentencepiece_model.pb.h"     // the reference's: -I<reference>/src/builtin_pb (NormalizerSpec, for the live spec edits)
 #include "sentencepiece_processor.h"   // the reference's: -I<reference>/src
 #include "spmx.h"
 
@@ -24,17 +27,13 @@ class AmdSentencePieceProcessor : public SentencePieceProcessor {
   util::Status LoadFromSerializedProto(absl::string_view serialized) override {                     // :261
     const util::Status st = SentencePieceProcessor::LoadFromSerializedProto(serialized);            // (keeps every other method working)
     if (!st.ok()) return st;
-    spmx_destroy(h_);
-    h_ = nullptr;
-    return ToStatus(spmx_create(serialized.data(), serialized.size(), device_, &h_), nullptr);
+    return Create(serialized.data(), serialized.size());
   }
   util::Status Load(absl::string_view filename) override {                                           // :245
     const util::Status st = SentencePieceProcessor::Load(filename);
     if (!st.ok()) return st;
     const std::string blob = serialized_model_proto();                                               // :694
-    spmx_destroy(h_);
-    h_ = nullptr;
-    return ToStatus(spmx_create(blob.data(), blob.size(), device_, &h_), nullptr);
+    return Create(blob.data(), blob.size());
   }
   util::Status SetEncodeExtraOptions(absl::string_view o) override {                                 // :267
     const util::Status st = SentencePieceProcessor::SetEncodeExtraOptions(o);
@@ -61,7 +60,8 @@ class AmdSentencePieceProcessor : public SentencePieceProcessor {
   }
   // the path itself: Encode(input, vector<int>*) (:299-300, .cc:392-403) on the device
   util::Status Encode(absl::string_view input, std::vector<int> *ids) const override {
-    const util::Status st = status();                      // CHECK_OR_RETURN_STATUS_STL (.cc:364-370)
+    util::Status st = status();                            // CHECK_OR_RETURN_STATUS_STL (.cc:364-370)
+    if (st.ok()) st = SyncNormalizerSpec();
     if (!st.ok()) return st;
     if (!ids) return util::Status(util::StatusCode::kInternal, "output container is null");
     ids->clear();
@@ -76,7 +76,8 @@ class AmdSentencePieceProcessor : public SentencePieceProcessor {
     return ToStatus(rc, h_);
   }
   util::Status Decode(const std::vector<int> &ids, std::string *detokenized) const override {       // :311-312
-    const util::Status st = status();
+    util::Status st = status();
+    if (st.ok()) st = SyncNormalizerSpec();
     if (!st.ok()) return st;
     if (!detokenized) return util::Status(util::StatusCode::kInternal, "output container is null");
     uint64_t n = 0;
@@ -91,16 +92,52 @@ class AmdSentencePieceProcessor : public SentencePieceProcessor {
   }
   // NEW: the batch form, element-wise Encode (sentencepiece.i:245-267): packed sentences in, CSR out (spmx_free)
   util::Status EncodeBatch(const char *text, const uint64_t *offsets, uint64_t n, int32_t **ids, uint64_t **id_offsets) const {
+    const util::Status st = SyncNormalizerSpec();
+    if (!st.ok()) return st;
     return ToStatus(spmx_encode_batch(h_, text, offsets, n, ids, id_offsets), h_);
   }
 
  private:
+  util::Status Create(const char *blob, size_t n) {
+    spmx_destroy(h_);
+    h_ = nullptr;
+    const util::Status st = ToStatus(spmx_create(blob, n, device_, &h_), nullptr);
+    if (st.ok()) pushed_.store(SpecBits(model_proto().normalizer_spec()), std::memory_order_release);
+    return st;
+  }
+  // mutable_normalizer_spec() (:699) is not virtual and hands out the base class's own proto: an edit through it -- also
+  // through a SentencePieceProcessor* -- is invisible here until the next call looks.  So every call on the path compares
+  // the three switches with what the handle was last given and pushes a difference as ONE override: the edit is live at
+  // the next Encode / Decode, as it is in the reference.  The edit itself (the header's "use at your own risk") is not to be
+  // made while calls are in flight; the calls AFTER it may come from any number of threads at once, as the const methods
+  // always may: the fast path is one acquire load and a compare, a thread that sees a difference takes the mutex, the first
+  // one in pushes the override, and pushed_ changes only once the handle's new tables are in place -- so every other thread
+  // either waits on the mutex and finds nothing left to do, or arrives later and reads tables that are complete.  No thread
+  // encodes while the handle is being rebuilt.
+  static int SpecBits(const NormalizerSpec &spec) {
+    return (spec.add_dummy_prefix() ? 1 : 0) | (spec.remove_extra_whitespaces() ? 2 : 0) | (spec.escape_whitespaces() ? 4 : 0);
+  }
+  util::Status SyncNormalizerSpec() const {
+    if (!h_) return util::Status();
+    const int now = SpecBits(model_proto().normalizer_spec());
+    if (now == pushed_.load(std::memory_order_acquire)) return util::Status();
+    std::lock_guard<std::mutex> lock(push_mu_);
+    if (now == pushed_.load(std::memory_order_relaxed)) return util::Status();      // another thread pushed it meanwhile
+    static const char *const kFields[3] = {"add_dummy_prefix", "remove_extra_whitespaces", "escape_whitespaces"};
+    const char *values[3] = {now & 1 ? "1" : "0", now & 2 ? "1" : "0", now & 4 ? "1" : "0"};
+    const int rc = spmx_override_normalizer_spec(h_, kFields, values, nullptr, 3);
+    if (rc != 0) return ToStatus(rc, h_);
+    pushed_.store(now, std::memory_order_release);
+    return util::Status();
+  }
   static util::Status ToStatus(int rc, const spmx_handle *h) {
     if (rc == 0) return util::Status();
     return util::Status(static_cast<util::StatusCode>(rc), spmx_last_error(h));
   }
   int device_ = 0;
   spmx_handle *h_ = nullptr;
+  mutable std::atomic<int> pushed_{7};            // the switches last pushed to the handle (SpecBits)
+  mutable std::mutex push_mu_;                    // one thread pushes a difference, the others wait for it
 };
 
 }  // namespace sentencepiece

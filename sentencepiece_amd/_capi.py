@@ -22,6 +22,8 @@ SYMBOLS = [
     ("spmx_set_decode_extra_options", C.c_int, [_H, C.c_char_p]),
     ("spmx_set_vocabulary", C.c_int, [_H, C.POINTER(C.c_char_p), C.POINTER(_U64), _U64]),
     ("spmx_reset_vocabulary", C.c_int, [_H]),
+    ("spmx_override_normalizer_spec", C.c_int, [_H, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(_U64), _U64]),
+    ("spmx_normalizer_spec", C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("spmx_piece_size", C.c_int, [_H]),
     ("spmx_piece_to_id", C.c_int, [_H, C.c_char_p, _U64]),
     ("spmx_id_to_piece", C.c_int64, [_H, C.c_int, C.c_char_p, _U64]),

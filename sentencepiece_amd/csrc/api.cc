@@ -276,15 +276,10 @@ struct Workspace {
 
 }  // namespace
 
-struct spmx_handle {
-  std::mutex mu;                 // the workspace pool, the last profile
-  ModelData model;
-  HostTables tables;
-  std::string extra_options;
-  std::string serialized;        // the ModelProto as it was loaded (serialized_model_proto, src/sentencepiece_processor.h:694)
-  int device = 0;
-  int n_cu = 256;
-  // device copies of the tables
+namespace spmx_tables {   // (a named namespace: spmx_handle, which the public header names, derives from it)
+// device copies of the model's tables: one set per handle; spmx_override_normalizer_spec uploads a second one beside it and
+// swaps the two when everything is there
+struct DevTables {
   DevBuf<uint32_t> d_ndarts, d_npair, d_sym_final, d_dec_info, d_dec_off;
   DevBuf<uint8_t> d_dec_bytes;
   DevBuf<uint8_t> d_nblob, d_plen;
@@ -294,6 +289,23 @@ struct spmx_handle {
   DevBuf<U2> d_utrie;
   DevBuf<uint16_t> d_sym_len;
   DevBuf<int32_t> d_byte_ids;
+  void FreeTables() {
+    d_ndarts.Free(); d_npair.Free(); d_sym_final.Free(); d_nblob.Free(); d_ptrie.Free(); d_chartab.Free();
+    d_pairtab.Free(); d_wordtab.Free(); d_utrie.Free(); d_sym_len.Free(); d_byte_ids.Free();
+    d_dec_info.Free(); d_dec_off.Free(); d_dec_bytes.Free(); d_plen.Free(); d_cfirst.Free(); d_umemo.Free(); d_umemo16.Free(); d_uall.Free(); d_udisp.Free(); d_uhot2.Free(); d_uhot.Free(); d_pscore.Free();
+  }
+};
+}  // namespace spmx_tables
+using spmx_tables::DevTables;
+
+struct spmx_handle : DevTables {
+  std::mutex mu;                 // the workspace pool, the last profile
+  ModelData model;
+  HostTables tables;
+  std::string extra_options;     // the SetEncodeExtraOptions string compiled into tables.scalars: a rebuild of the tables compiles it again
+  std::string serialized;        // the ModelProto of the handle: as loaded, then with every normalizer_spec override patched in (serialized_model_proto, src/sentencepiece_processor.h:694)
+  int device = 0;
+  int n_cu = 256;
   SpmxDev dev{};   // scalars + device pointers
   // the denormalizer (denormalizer_spec with a charsmap): normalizer tables of its own
   HostTables dn_tables;
@@ -346,7 +358,8 @@ struct spmx_handle {
   bool no_uni_wave = false;      // SPMX_NO_UNI_WAVE=1: unigram models never take the wave-cooperative form (kernels_uniwave.h)
   uint32_t uni_wave_max = 0;     // SPMX_UNI_WAVE_MAX: a staged class with fewer sentences than this takes the wave-cooperative form
   int word_wgs = 1;              // SPMX_WORD_WGS: workgroups per CU of the word kernel's first pass
-  uint64_t table_bytes = 0;      // device bytes of the tables uploaded at load (spmx_handle_info)
+  uint64_t table_bytes = 0;      // device bytes of the handle's tables (spmx_handle_info): as uploaded at load, or by the last override
+  uint64_t dn_table_bytes = 0;   // ... of which the denormalizer's
   double load_ms = 0.0;          // parse + table build + upload, wall clock
   int word_form = 3;             // SPMX_WORD_WAVE: which word rounds take the word-per-lane form (kernels_wordwave.h): bit 0 the first, bit 1 the second; 0: the sentence-per-lane loops
   int wordwave_waves = 14;       // SPMX_WORDWAVE_WAVES: wavefronts per workgroup of the word-per-lane kernels (C2's first round: 8 -> 3.71 ms, 10 -> 3.31, 12 -> 3.08, 13 -> 3.02, 14 -> 2.96, 15 -> 2.94 with a worse step; 14 x 10 KB + the shared tables = 153 KB of LDS)
@@ -423,68 +436,71 @@ hipError_t Upload(DevBuf<T> *b, const std::vector<T> &v) {
   return hipMemcpy(b->p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-// Uploads every table and binds h->dev to the device copies.
-int UploadTables(spmx_handle *h) {
-  HostTables &t = h->tables;
-  HIP_OR_RETURN(h, Upload(&h->d_ndarts, t.ndarts));
-  HIP_OR_RETURN(h, Upload(&h->d_nblob, t.nblob));
-  HIP_OR_RETURN(h, Upload(&h->d_npair, t.npair));
-  HIP_OR_RETURN(h, Upload(&h->d_ptrie, t.ptrie));
-  HIP_OR_RETURN(h, Upload(&h->d_cfirst, t.cfirst));
-  HIP_OR_RETURN(h, Upload(&h->d_plen, t.plen));
-  HIP_OR_RETURN(h, Upload(&h->d_utrie, t.utrie));
-  HIP_OR_RETURN(h, Upload(&h->d_chartab, t.chartab));
-  HIP_OR_RETURN(h, Upload(&h->d_pairtab, t.pairtab));
-  HIP_OR_RETURN(h, Upload(&h->d_wordtab, t.wordtab));
-  HIP_OR_RETURN(h, Upload(&h->d_umemo, t.umemo));
-  HIP_OR_RETURN(h, Upload(&h->d_umemo16, t.umemo16));
-  HIP_OR_RETURN(h, Upload(&h->d_uall, t.uall));
-  HIP_OR_RETURN(h, Upload(&h->d_udisp, t.udisp));
-  HIP_OR_RETURN(h, Upload(&h->d_uhot2, t.uhot2));
-  HIP_OR_RETURN(h, Upload(&h->d_uhot, t.uhot));
-  HIP_OR_RETURN(h, Upload(&h->d_pscore, t.pscore));
-  HIP_OR_RETURN(h, Upload(&h->d_sym_final, t.sym_final));
-  HIP_OR_RETURN(h, Upload(&h->d_sym_len, t.sym_len));
-  HIP_OR_RETURN(h, Upload(&h->d_byte_ids, t.byte_ids));
-  HIP_OR_RETURN(h, Upload(&h->d_dec_info, t.dec_info));
-  HIP_OR_RETURN(h, Upload(&h->d_dec_off, t.dec_off));
-  HIP_OR_RETURN(h, Upload(&h->d_dec_bytes, t.dec_bytes));
-  h->dev = t.scalars;
-  h->dev.ndarts = h->d_ndarts.p;
-  h->dev.nblob = h->d_nblob.p;
-  h->dev.npair = h->d_npair.p;
-  h->dev.ptrie = h->d_ptrie.p;
-  h->dev.cfirst = t.cfirst.empty() ? nullptr : h->d_cfirst.p;
-  h->dev.plen = h->d_plen.p;
-  h->dev.utrie = h->d_utrie.p;
-  h->dev.chartab = h->d_chartab.p;
-  h->dev.pairtab = h->d_pairtab.p;
-  h->dev.wordtab = h->d_wordtab.p;
-  h->dev.umemo = h->d_umemo.p;
-  h->dev.umemo16 = h->d_umemo16.p;
-  h->dev.uall = h->d_uall.p;
-  h->dev.udisp = h->d_udisp.p;
-  h->dev.uhot2 = h->d_uhot2.p;
-  h->dev.uhot = h->d_uhot.p;
-  h->dev.pscore = h->d_pscore.p;
-  h->dev.sym_final = h->d_sym_final.p;
-  h->dev.sym_len = h->d_sym_len.p;
-  h->dev.byte_ids = h->d_byte_ids.p;
-  h->dev.dec_info = h->d_dec_info.p;
-  h->dev.dec_off = h->d_dec_off.p;
-  h->dev.dec_bytes = h->d_dec_bytes.p;
-  if (h->model.has_denormalizer) {
-    const HostTables &d = h->dn_tables;
-    HIP_OR_RETURN(h, Upload(&h->dn_ndarts, d.ndarts));
-    HIP_OR_RETURN(h, Upload(&h->dn_nblob, d.nblob));
-    HIP_OR_RETURN(h, Upload(&h->dn_npair, d.npair));
-    HIP_OR_RETURN(h, Upload(&h->dn_utrie, d.utrie));
-    h->dn_dev = d.scalars;
-    h->dn_dev.ndarts = h->dn_ndarts.p;
-    h->dn_dev.nblob = h->dn_nblob.p;
-    h->dn_dev.npair = h->dn_npair.p;
-    h->dn_dev.utrie = h->dn_utrie.p;
-  }
+// Uploads every table of t into d and binds *dev (t's scalars) to the device copies.
+int UploadTables(spmx_handle *eh, DevTables *d, const HostTables &t, SpmxDev *dev) {
+  HIP_OR_RETURN(eh, Upload(&d->d_ndarts, t.ndarts));
+  HIP_OR_RETURN(eh, Upload(&d->d_nblob, t.nblob));
+  HIP_OR_RETURN(eh, Upload(&d->d_npair, t.npair));
+  HIP_OR_RETURN(eh, Upload(&d->d_ptrie, t.ptrie));
+  HIP_OR_RETURN(eh, Upload(&d->d_cfirst, t.cfirst));
+  HIP_OR_RETURN(eh, Upload(&d->d_plen, t.plen));
+  HIP_OR_RETURN(eh, Upload(&d->d_utrie, t.utrie));
+  HIP_OR_RETURN(eh, Upload(&d->d_chartab, t.chartab));
+  HIP_OR_RETURN(eh, Upload(&d->d_pairtab, t.pairtab));
+  HIP_OR_RETURN(eh, Upload(&d->d_wordtab, t.wordtab));
+  HIP_OR_RETURN(eh, Upload(&d->d_umemo, t.umemo));
+  HIP_OR_RETURN(eh, Upload(&d->d_umemo16, t.umemo16));
+  HIP_OR_RETURN(eh, Upload(&d->d_uall, t.uall));
+  HIP_OR_RETURN(eh, Upload(&d->d_udisp, t.udisp));
+  HIP_OR_RETURN(eh, Upload(&d->d_uhot2, t.uhot2));
+  HIP_OR_RETURN(eh, Upload(&d->d_uhot, t.uhot));
+  HIP_OR_RETURN(eh, Upload(&d->d_pscore, t.pscore));
+  HIP_OR_RETURN(eh, Upload(&d->d_sym_final, t.sym_final));
+  HIP_OR_RETURN(eh, Upload(&d->d_sym_len, t.sym_len));
+  HIP_OR_RETURN(eh, Upload(&d->d_byte_ids, t.byte_ids));
+  HIP_OR_RETURN(eh, Upload(&d->d_dec_info, t.dec_info));
+  HIP_OR_RETURN(eh, Upload(&d->d_dec_off, t.dec_off));
+  HIP_OR_RETURN(eh, Upload(&d->d_dec_bytes, t.dec_bytes));
+  *dev = t.scalars;
+  dev->ndarts = d->d_ndarts.p;
+  dev->nblob = d->d_nblob.p;
+  dev->npair = d->d_npair.p;
+  dev->ptrie = d->d_ptrie.p;
+  dev->cfirst = t.cfirst.empty() ? nullptr : d->d_cfirst.p;
+  dev->plen = d->d_plen.p;
+  dev->utrie = d->d_utrie.p;
+  dev->chartab = d->d_chartab.p;
+  dev->pairtab = d->d_pairtab.p;
+  dev->wordtab = d->d_wordtab.p;
+  dev->umemo = d->d_umemo.p;
+  dev->umemo16 = d->d_umemo16.p;
+  dev->uall = d->d_uall.p;
+  dev->udisp = d->d_udisp.p;
+  dev->uhot2 = d->d_uhot2.p;
+  dev->uhot = d->d_uhot.p;
+  dev->pscore = d->d_pscore.p;
+  dev->sym_final = d->d_sym_final.p;
+  dev->sym_len = d->d_sym_len.p;
+  dev->byte_ids = d->d_byte_ids.p;
+  dev->dec_info = d->d_dec_info.p;
+  dev->dec_off = d->d_dec_off.p;
+  dev->dec_bytes = d->d_dec_bytes.p;
+  return kOk;
+}
+
+// The denormalizer's tables (a model with a denormalizer_spec): uploaded once, at load; no override touches them.
+int UploadDenormTables(spmx_handle *h) {
+  if (!h->model.has_denormalizer) return kOk;
+  const HostTables &d = h->dn_tables;
+  HIP_OR_RETURN(h, Upload(&h->dn_ndarts, d.ndarts));
+  HIP_OR_RETURN(h, Upload(&h->dn_nblob, d.nblob));
+  HIP_OR_RETURN(h, Upload(&h->dn_npair, d.npair));
+  HIP_OR_RETURN(h, Upload(&h->dn_utrie, d.utrie));
+  h->dn_dev = d.scalars;
+  h->dn_dev.ndarts = h->dn_ndarts.p;
+  h->dn_dev.nblob = h->dn_nblob.p;
+  h->dn_dev.npair = h->dn_npair.p;
+  h->dn_dev.utrie = h->dn_utrie.p;
   return kOk;
 }
 
@@ -525,9 +541,7 @@ int RefreshDevice(spmx_handle *h, bool types_changed) {
 void DestroyHandle(spmx_handle *h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  h->d_ndarts.Free(); h->d_npair.Free(); h->d_sym_final.Free(); h->d_nblob.Free(); h->d_ptrie.Free(); h->d_chartab.Free();
-  h->d_pairtab.Free(); h->d_wordtab.Free(); h->d_utrie.Free(); h->d_sym_len.Free(); h->d_byte_ids.Free();
-  h->d_dec_info.Free(); h->d_dec_off.Free(); h->d_dec_bytes.Free(); h->d_plen.Free(); h->d_cfirst.Free(); h->d_umemo.Free(); h->d_umemo16.Free(); h->d_uall.Free(); h->d_udisp.Free(); h->d_uhot2.Free(); h->d_uhot.Free(); h->d_pscore.Free();
+  h->FreeTables();
   h->dn_ndarts.Free(); h->dn_npair.Free(); h->dn_nblob.Free(); h->dn_utrie.Free();
   h->pool.clear();
   delete h;
@@ -1829,8 +1843,11 @@ int spmx_create(const void *model_bytes, uint64_t n_bytes, int device, spmx_hand
       }
     }
     t_upload_bytes = 0;
-    if (int rc = UploadTables(h.get()); rc != kOk) return rc;
+    if (int rc = UploadTables(nullptr, h.get(), h->tables, &h->dev); rc != kOk) return rc;
+    const uint64_t model_table_bytes = t_upload_bytes;
+    if (int rc = UploadDenormTables(h.get()); rc != kOk) return rc;
     h->table_bytes = t_upload_bytes;
+    h->dn_table_bytes = t_upload_bytes - model_table_bytes;
     h->load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_load0).count();
     if (!h->model.self_test.empty())                        // "Running self-testing." (sentencepiece_processor.cc:259-278)
       if (int rc = RunSelfTest(h.get()); rc != kOk) return rc;
@@ -1858,6 +1875,7 @@ int spmx_set_encode_extra_options(spmx_handle *h, const char *options) {
   return Guard(h, [&]() -> int {
     Status st = CompileExtraOptions(h->model, options ? options : "", &h->tables);
     if (!st.ok()) return Fail(h, st.code, st.message);
+    h->extra_options = options ? options : "";
     HIP_OR_RETURN(h, hipSetDevice(h->device));
     return RefreshDevice(h, false);
   });
@@ -1906,6 +1924,104 @@ int spmx_reset_vocabulary(spmx_handle *h) {
     HIP_OR_RETURN(h, hipSetDevice(h->device));
     return RefreshDevice(h, true);
   });
+}
+
+namespace {
+
+// mutable_normalizer_spec() edits on a live handle: CompileTables + UploadTables for the new spec, beside the tables the
+// kernels read, and a swap once both have succeeded -- a failure on the way (host memory, device memory, a charsmap blob
+// Load would refuse) leaves the handle as it was.  What a load derives from the spec and this has to derive again:
+//   tables / dev / the device buffers      compiled and uploaded here (kNfCompressSp, the launch shape, the word memo, the
+//                                          score ring and the split form's sizes are all read from h->tables per call)
+//   SetVocabulary's piece types            live in h->model; CompileTables ends with RefreshTypeFlags over them
+//   the encode extra options               compiled into the new scalars from h->extra_options
+//   word_backoff                           a verdict on the OLD tables' word rounds: cleared
+//   table_bytes                            measured again
+// and what does not depend on it: the decode extra options (dx_*), the profiling switch, the denormalizer's tables, the
+// environment switches, the class table, and the pooled workspaces (buffers sized per call, no table-derived state; the
+// call-local word memo is cleared by every call that uses it).
+int RebuildForSpec(spmx_handle *h, bool add_dummy_prefix, bool remove_extra_ws, bool escape_ws, std::string *charsmap) {
+  ModelData &m = h->model;
+  struct Undo {                     // the model keeps the new spec only when everything went through
+    ModelData &m;
+    bool adp, rew, esc, done = false;
+    std::string *charsmap;
+    ~Undo() {
+      if (done) return;
+      m.add_dummy_prefix = adp; m.remove_extra_ws = rew; m.escape_ws = esc;
+      if (charsmap) m.charsmap.swap(*charsmap);
+    }
+  } undo{m, m.add_dummy_prefix, m.remove_extra_ws, m.escape_ws, false, charsmap};
+  m.add_dummy_prefix = add_dummy_prefix; m.remove_extra_ws = remove_extra_ws; m.escape_ws = escape_ws;
+  if (charsmap) m.charsmap.swap(*charsmap);
+  std::unique_ptr<HostTables> nt(new HostTables);
+  Status st = CompileTables(m, nt.get());
+  if (st.ok()) st = CompileExtraOptions(m, h->extra_options, nt.get());
+  if (!st.ok()) return Fail(h, st.code, st.message);
+  HIP_OR_RETURN(h, hipSetDevice(h->device));
+  DevTables fresh;
+  SpmxDev dev{};
+  t_upload_bytes = 0;
+  if (int rc = UploadTables(h, &fresh, *nt, &dev); rc != kOk) {
+    fresh.FreeTables();
+    return rc;
+  }
+  std::swap(static_cast<DevTables &>(*h), fresh);
+  fresh.FreeTables();               // the old set (hipFree waits for the device: nothing reads it any more)
+  h->tables = std::move(*nt);
+  h->dev = dev;
+  h->table_bytes = t_upload_bytes + h->dn_table_bytes;
+  h->word_backoff.store(0, std::memory_order_relaxed);
+  undo.done = true;
+  return kOk;
+}
+
+}  // namespace
+
+int spmx_override_normalizer_spec(spmx_handle *h, const char *const *fields, const char *const *values,
+                                  const uint64_t *value_lens, uint64_t n) {
+  if (!h) return kInvalidArgument;
+  return Guard(h, [&]() -> int {
+    if (n && (!fields || !values)) return Fail(h, kInvalidArgument, "null field or value array");
+    // the reference's loop (sentencepiece.i:706-716) applies pair after pair and returns at the first that fails: the
+    // pairs before it stay applied
+    std::vector<SpecEdit> edits;
+    Status failed;
+    for (uint64_t i = 0; i < n && failed.ok(); ++i) {
+      const char *v = values[i] ? values[i] : "";
+      SpecEdit e;
+      failed = ParseSpecEdit(fields[i] ? fields[i] : "", std::string(v, value_lens ? value_lens[i] : strlen(v)), &e);
+      if (failed.ok()) edits.push_back(std::move(e));
+    }
+    if (!edits.empty()) {
+      bool adp = h->model.add_dummy_prefix, rew = h->model.remove_extra_ws, esc = h->model.escape_ws;
+      const std::string *cm = nullptr;
+      for (const SpecEdit &e : edits) {
+        if (e.field == 2) cm = &e.bytes;
+        else if (e.field == 3) adp = e.flag;
+        else if (e.field == 4) rew = e.flag;
+        else if (e.field == 5) esc = e.flag;
+      }
+      if (cm && *cm == h->model.charsmap) cm = nullptr;
+      std::string patched;
+      Status ps = PatchNormalizerSpec(h->serialized, edits, &patched);
+      if (!ps.ok()) return Fail(h, ps.code, ps.message);
+      if (cm || adp != h->model.add_dummy_prefix || rew != h->model.remove_extra_ws || esc != h->model.escape_ws) {
+        std::string charsmap = cm ? *cm : std::string();
+        if (int rc = RebuildForSpec(h, adp, rew, esc, cm ? &charsmap : nullptr); rc != kOk) return rc;
+      }
+      h->serialized.swap(patched);
+    }
+    return failed.ok() ? kOk : Fail(h, failed.code, failed.message);
+  });
+}
+
+int spmx_normalizer_spec(const spmx_handle *h, int *add_dummy_prefix, int *remove_extra_whitespaces, int *escape_whitespaces) {
+  if (!h) return kInvalidArgument;
+  if (add_dummy_prefix) *add_dummy_prefix = h->model.add_dummy_prefix ? 1 : 0;
+  if (remove_extra_whitespaces) *remove_extra_whitespaces = h->model.remove_extra_ws ? 1 : 0;
+  if (escape_whitespaces) *escape_whitespaces = h->model.escape_ws ? 1 : 0;
+  return kOk;
 }
 
 int spmx_piece_size(const spmx_handle *h) { return h ? static_cast<int>(h->model.pieces.size()) : 0; }

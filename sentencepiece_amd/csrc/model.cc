@@ -1,5 +1,6 @@
 #include "model.h"
 
+#include <cctype>
 #include <cfloat>
 #include <cstdio>
 #include <cstring>
@@ -185,6 +186,84 @@ Status InitializeModel(ModelData *m) {
     }
   }
   if (m->model_type == kUnigram && m->pieces_map.empty()) return Status::Error(kInternal, "no pieces are loaded.");
+  return Status::OK();
+}
+
+Status ParseSpecEdit(const std::string &name, const std::string &value, SpecEdit *out) {
+  static const char *const kNames[] = {"name", "precompiled_charsmap", "add_dummy_prefix", "remove_extra_whitespaces",
+                                       "escape_whitespaces", "normalization_rule_tsv"};
+  out->field = 0;
+  for (int f = 0; f < 6; ++f)
+    if (name == kNames[f]) out->field = f + 1;
+  if (out->field == 0) return Status::Error(kNotFound, "unknown field name \"" + name + "\" in NormalizerSpec.");
+  if (out->field < 3 || out->field > 5) {
+    out->bytes = value;
+    return Status::OK();
+  }
+  std::string lower = value.empty() ? std::string("true") : value;
+  for (char &c : lower) c = static_cast<char>(tolower(static_cast<unsigned char>(c)));
+  for (const char *t : {"1", "t", "true", "y", "yes"})
+    if (lower == t) { out->flag = true; return Status::OK(); }
+  for (const char *f : {"0", "f", "false", "n", "no"})
+    if (lower == f) { out->flag = false; return Status::OK(); }
+  return Status::Error(kInvalidArgument, "cannot parse \"" + value + "\" as bool.");
+}
+
+namespace {
+
+void PutVarint(uint64_t v, std::string *out) {
+  while (v >= 0x80) { out->push_back(static_cast<char>(v | 0x80)); v >>= 7; }
+  out->push_back(static_cast<char>(v));
+}
+
+}  // namespace
+
+Status PatchNormalizerSpec(const std::string &proto, const std::vector<SpecEdit> &edits, std::string *out) {
+  bool edited[7] = {false};
+  for (const SpecEdit &e : edits) edited[e.field] = true;
+  // the spec's own bytes without the edited fields.  A submessage that comes in several parts is the merge of the parts,
+  // which for these fields (all optional scalars) is their concatenation; the result goes where the first part was
+  const uint8_t *b = reinterpret_cast<const uint8_t *>(proto.data());
+  std::string spec, head, tail;
+  bool seen = false;
+  {
+    Cursor c{b, b + proto.size()};
+    int wt; uint64_t v = 0; const uint8_t *s = nullptr; size_t sl = 0;
+    for (const uint8_t *at = c.p; int f = c.Next(&wt, &v, &s, &sl); at = c.p) {
+      if (f != 3 || wt != 2) {
+        (seen ? tail : head).append(reinterpret_cast<const char *>(at), static_cast<size_t>(c.p - at));
+        continue;
+      }
+      seen = true;
+      Cursor t{s, s + sl};
+      const uint8_t *ts = nullptr; size_t tl = 0;
+      for (const uint8_t *ft = t.p; int g = t.Next(&wt, &v, &ts, &tl); ft = t.p)
+        if (g < 1 || g > 6 || !edited[g]) spec.append(reinterpret_cast<const char *>(ft), static_cast<size_t>(t.p - ft));
+      if (t.bad || t.p != t.end) c.bad = true;
+    }
+    // (Next also stops, without `bad`, at a key with field number 0: nothing behind it may be dropped silently)
+    if (c.bad || c.p != c.end) return Status::Error(kInternal, "could not parse ModelProto");
+  }
+  for (int f = 1; f <= 6; ++f) {
+    if (!edited[f]) continue;
+    const SpecEdit *last = nullptr;
+    for (const SpecEdit &e : edits) if (e.field == f) last = &e;
+    if (f >= 3 && f <= 5) {
+      spec.push_back(static_cast<char>(f << 3));
+      spec.push_back(last->flag ? 1 : 0);
+    } else {
+      spec.push_back(static_cast<char>(f << 3 | 2));
+      PutVarint(last->bytes.size(), &spec);
+      spec += last->bytes;
+    }
+  }
+  out->clear();
+  out->reserve(proto.size() + spec.size() + 16);
+  *out += head;
+  out->push_back(static_cast<char>(3 << 3 | 2));
+  PutVarint(spec.size(), out);
+  *out += spec;
+  *out += tail;
   return Status::OK();
 }
 

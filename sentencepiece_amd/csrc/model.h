@@ -73,6 +73,22 @@ Status InitializeModel(ModelData *m);
 Status SetVocabulary(ModelData *m, const std::vector<std::string> &valid);
 Status ResetVocabulary(ModelData *m);
 
+// One (name, value) pair of SentencePieceTrainer::SetProtoField(name, value, NormalizerSpec *) (src/spec_parser.h:256-270)
+// after parsing: the NormalizerSpec field number (sentencepiece_model.proto:245-274: 1 name, 2 precompiled_charsmap,
+// 3 add_dummy_prefix, 4 remove_extra_whitespaces, 5 escape_whitespaces, 6 normalization_rule_tsv) and its value.
+struct SpecEdit {
+  int field = 0;
+  bool flag = false;     // fields 3 .. 5
+  std::string bytes;     // fields 1, 2, 6
+};
+// NOT_FOUND "unknown field name ..." / INVALID_ARGUMENT "cannot parse ... as bool." with the reference's texts; booleans
+// as string_util::lexical_cast<bool> reads them (src/util.h:60-77), an empty value meaning true (PARSE_BOOL).
+Status ParseSpecEdit(const std::string &name, const std::string &value, SpecEdit *out);
+// The ModelProto `proto` with the edits applied to its normalizer_spec (field 3), as set_x() on mutable_normalizer_spec()
+// followed by SerializeAsString would leave it: an edited field is written explicitly, also at its default value; every
+// other byte -- unknown fields included -- is kept; a proto without the submessage gets one.
+Status PatchNormalizerSpec(const std::string &proto, const std::vector<SpecEdit> &edits, std::string *out);
+
 inline int OneCharLen(unsigned char c) {  // src/util.h:151-153
   return "\1\1\1\1\1\1\1\1\1\1\1\1\2\2\3\4"[c >> 4];
 }

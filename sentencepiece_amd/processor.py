@@ -73,7 +73,7 @@ class SentencePieceProcessor:
         self._h = h
         self._pid = os.getpid()
         self._extra = self._applied = ""
-        self._model_proto = bytes(model_proto)
+        self._model_proto = bytes(model_proto)      # as loaded: the piece scores (GetScore) come from here
         return True
 
     LoadFromSerializedProto = lambda self, proto: self.Load(model_proto=proto)  # noqa: E731
@@ -87,9 +87,54 @@ class SentencePieceProcessor:
     load_from_file = LoadFromFile
 
     def serialized_model_proto(self):
-        """The ModelProto the processor was loaded from (src/sentencepiece_processor.h:667)."""
+        """``serialized_model_proto()`` (src/sentencepiece_processor.h:694): the handle's current ModelProto -- the bytes
+        the processor was loaded from with every ``OverrideNormalizerSpec`` edit patched in."""
         self._need()
-        return self._model_proto
+        p, n = C.c_char_p(), C.c_uint64(0)
+        self._check(self._lib.spmx_serialized_model(self._h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value)
+
+    def OverrideNormalizerSpec(self, **kwargs):
+        """``OverrideNormalizerSpec(**kwargs)`` (python/src/sentencepiece/__init__.py:917-921, sentencepiece.i:706-716):
+        ``SetProtoField(name, str(value))`` on the live normalizer_spec, pair after pair, in one C call -- one rebuild of
+        the device tables.  ``sp.OverrideNormalizerSpec(add_dummy_prefix=False)``.  Errors as the wrapper's SWIG layer maps
+        them (sentencepiece.i:70-82): an unknown field is an ``OSError``, an unparsable value a ``SyntaxError``, anything
+        else a ``RuntimeError``; the pairs before the failing one stay applied.  A ``bytes`` value (a
+        ``precompiled_charsmap``) is passed as it is -- ``str()`` of one could never be meant."""
+        self._need()
+        names = [k.encode("utf-8") for k in kwargs]
+        vals = [bytes(v) if isinstance(v, (bytes, bytearray)) else str(v).encode("utf-8") for v in kwargs.values()]
+        n = len(names)
+        lens = (C.c_uint64 * n)(*[len(v) for v in vals])
+        bufs = [C.create_string_buffer(v, len(v) + 1) for v in vals]      # (bytes with inner zeros keep their length)
+        rc = self._lib.spmx_override_normalizer_spec(
+            self._h, (C.c_char_p * n)(*names), (C.c_char_p * n)(*[C.cast(b, C.c_char_p) for b in bufs]), lens, n)
+        if rc != _OK:
+            msg = self._lib.spmx_last_error(self._h).decode("utf-8", "replace")
+            raise {5: OSError, 3: SyntaxError}.get(rc, RuntimeError)(msg)
+        return True
+
+    override_normalizer_spec = OverrideNormalizerSpec
+
+    def NormalizerSpec(self):
+        """dict(add_dummy_prefix, remove_extra_whitespaces, escape_whitespaces): the switches the handle applies now."""
+        self._need()
+        a, r, e = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.spmx_normalizer_spec(self._h, C.byref(a), C.byref(r), C.byref(e)))
+        return {"add_dummy_prefix": bool(a.value), "remove_extra_whitespaces": bool(r.value), "escape_whitespaces": bool(e.value)}
+
+    # pickling (python/src/sentencepiece/__init__.py:932-946; sentencepiece.i:1228-1243): the state IS the ModelProto, so
+    # an override travels with it; extra options and a vocabulary restriction do not, as in the reference.  The copy is
+    # loaded on device 0: a worker pinned to another GPU loads the state itself, Load(model_proto=state) with device=.
+    def __getstate__(self):
+        return self.serialized_model_proto()
+
+    def __setstate__(self, serialized_model_proto):
+        self.__init__()
+        self.LoadFromSerializedProto(serialized_model_proto)
+
+    def __getitem__(self, piece):
+        return self.PieceToId(piece)
 
     def _close(self):
         if self._h:
