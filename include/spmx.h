@@ -93,7 +93,7 @@ int spmx_piece_type(const spmx_handle *h, int id);
 int spmx_bos_id(const spmx_handle *h);
 int spmx_eos_id(const spmx_handle *h);
 int spmx_pad_id(const spmx_handle *h);
-int spmx_model_type(const spmx_handle *h);   /* 1 unigram, 2 bpe */
+int spmx_model_type(const spmx_handle *h);   /* trainer_spec.model_type: 1 unigram, 2 bpe, 3 word, 4 char */
 /* Diagnostic: the kNf* bits the table compiler derived for this model (csrc/dev.h): which normalizer switches are on,
  * whether the one-byte space symbol / the word-wise BPE form apply. */
 uint32_t spmx_model_flags(const spmx_handle *h);

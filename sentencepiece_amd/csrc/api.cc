@@ -547,6 +547,15 @@ void DestroyHandle(spmx_handle *h) {
   delete h;
 }
 
+// First guess at the ids of a batch (a call whose ids outgrow it runs again with the exact count): subword and word
+// models give fewer than one id per two bytes; a character model about one per byte -- one per character, the dummy
+// prefix and the extra ids per sentence -- and so does a word model with byte fallback on text outside its vocabulary
+// (every unknown word is its bytes).
+uint64_t IdsGuess(const spmx_handle *h, uint64_t text_bytes, uint64_t n) {
+  const bool per_byte = h->model.model_type == kChar || (h->model.model_type == kWord && h->model.byte_fallback);
+  return per_byte ? text_bytes + 6 * n + 64 : text_bytes / 2 + 4 * n + 64;
+}
+
 // score-ring entries of the streaming unigram kernels for this handle's model
 uint32_t HandleRing(const spmx_handle *h) {
   const uint32_t r = ScoreRing(h->tables.max_piece_len);
@@ -613,7 +622,7 @@ StreamPlan PlanStream(const spmx_handle *h, EncodeArgs *a, const uint32_t *count
   const bool bp_short = model == kUnigram && !(h->dev.flags & kNfHasUserDefined) &&
                         h->model.pieces.size() <= kBpShortMaxVocab && !h->no_bp_short;
   a->bp_short = bp_short ? 1u : 0u;
-  const uint32_t bpsz = bp_short ? 2u : 4u;
+  const uint32_t bpsz = (model == kWord || model == kChar) ? 0u : bp_short ? 2u : 4u;   // (word / char: no back-pointer blocks in the slab)
   uint32_t priv = StreamPrivateBytes(model, ring, bpsz);
   // the split form (kernels_matchfold.h) for the classes of long sentences of a unigram model: its match phase keeps ONE
   // sentence's raw and normalized image in the wavefront's LDS
@@ -771,6 +780,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     word_ok = false;
   }
   const bool is_bpe = h->model.model_type == kBpe;
+  const bool cw_model = h->model.model_type == kWord || h->model.model_type == kChar;
   // streaming (lane-per-sentence) kernels: every unigram model; BPE models that can be segmented word by word
   const bool dropout = is_bpe && ws->bpe_dropout > 0.f;      // BPE-dropout: every sentence takes the long form
   const bool bpe_stream = is_bpe && (h->dev.flags & kNfBpeWordwise) && !(h->dev.flags & kNfHasUnused) && !h->no_stream && !dropout;
@@ -873,6 +883,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     for (bool &u : ws->slot_used) u = false;
     uint32_t known[kMaxClasses] = {0};       // the class lists: every sentence, or (scanned) the plain ones
     uint32_t gen_known[kMaxClasses] = {0};   // (scanned) the sentences set aside for the general kernels
+    uint32_t align_known[kMaxClasses] = {0};
     uint64_t gen_total = 0;
     if (!direct) {
       if (int rc = RunClassify(h, ws, d_offsets, n32, stream, scanned ? d_text : nullptr, text_bytes, scanned ? gen_lists : nullptr); rc != kOk) return rc;
@@ -925,7 +936,8 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       const uint64_t slab_total = static_cast<uint64_t>(sp.grid) * sp.waves * sp.slab_bytes;
       HIP_OR_RETURN(h, ws->d_slab.Reserve(slab_total));
       la.slab = ws->d_slab.p;
-      snprintf(ws->slot_name[slot], sizeof(ws->slot_name[slot]), "%s", is_bpe ? "EncodeBpeStreamKernel" : la.bp_short ? (la.ring == 16 ? "EncodeStreamShortKernel<16>" : "EncodeStreamShortKernel<0>")
+      snprintf(ws->slot_name[slot], sizeof(ws->slot_name[slot]), "%s", h->model.model_type == kWord ? "EncodeWordModelStreamKernel"
+               : h->model.model_type == kChar ? (uds ? "EncodeCharStreamKernel<true>" : "EncodeCharStreamKernel<false>") : is_bpe ? "EncodeBpeStreamKernel" : la.bp_short ? (la.ring == 16 ? "EncodeStreamShortKernel<16>" : "EncodeStreamShortKernel<0>")
                : (la.ring == 16 ? (uds ? "EncodeStreamKernel<16, true>" : "EncodeStreamKernel<16, false>")
                                 : (uds ? "EncodeStreamKernel<0, true>" : "EncodeStreamKernel<0, false>")));
       HIP_OR_RETURN(h, record(slot, 0));
@@ -933,7 +945,10 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
         snprintf(ws->slot_name[slot], sizeof(ws->slot_name[slot]), "%s", la.bp_short ? "EncodeSplitShortKernel" : "EncodeSplitKernel");
         HIP_OR_RETURN(h, LaunchEncodeSplit(la, sp.grid, sp.waves, sp.lds, stream));
       } else {
-        HIP_OR_RETURN(h, LaunchEncodeStream(h->model.model_type, uds, la, sp.grid, sp.waves, sp.lds, stream));
+        if (h->model.model_type == kWord || h->model.model_type == kChar)
+          HIP_OR_RETURN(h, LaunchEncodeCharWord(h->model.model_type, uds, la, sp.grid, sp.waves, sp.lds, stream));
+        else
+          HIP_OR_RETURN(h, LaunchEncodeStream(h->model.model_type, uds, la, sp.grid, sp.waves, sp.lds, stream));
       }
       HIP_OR_RETURN(h, record(slot, 1));
       ws->slot_used[slot] = true;
@@ -941,7 +956,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     };
     // which classes a launch of split tiles takes (PlanStream decides again, from the same rules)
     auto split_launch_class = [&](int c) -> bool {
-      return !is_bpe && h->tables.split_ok && !h->no_split && !uds && cls[c].rcap > h->split_min_raw && cls[c].rcap <= kMfMaxRaw &&
+      return h->model.model_type == kUnigram && h->tables.split_ok && !h->no_split && !uds && cls[c].rcap > h->split_min_raw && cls[c].rcap <= kMfMaxRaw &&
              !((h->dev.flags & kNfEscapeWs) && !(h->dev.flags & kNfCompressSp) && 2u * cls[c].rcap + 64u >= 65000u);
     };
     // the long form over one device-side list (BPE), growing the slice pool until every sentence has had its turn
@@ -971,12 +986,13 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
         HIP_OR_RETURN(h, hipMemsetAsync(&ws->d_ctrl->retry_count[turn], 0, sizeof(uint32_t), stream));
         uint64_t g = uni ? static_cast<uint64_t>(left) : (static_cast<uint64_t>(left) + 63) / 64;   // a sentence per wave / per lane
         if (g > static_cast<uint64_t>(h->n_cu) * 16) g = static_cast<uint64_t>(h->n_cu) * 16;
-        snprintf(ws->slot_name[kSlotLong], sizeof(ws->slot_name[kSlotLong]), uni ? "UniLongKernel" : "BpeLongKernel");
+        snprintf(ws->slot_name[kSlotLong], sizeof(ws->slot_name[kSlotLong]), cw_model ? "CharWordWaveKernel" : uni ? "UniLongKernel" : "BpeLongKernel");
         if (!ws->slot_used[kSlotLong]) HIP_OR_RETURN(h, record(kSlotLong, 0));
         // few, long documents: a workgroup of two wavefronts each (a walker and a folder side by side); many: a wavefront each
-        const bool pipe = uni && h->uw_pipe != 0 && (h->uw_pipe == 2 || (left <= static_cast<uint32_t>(h->n_cu) * 4u && text_bytes / n >= 4096u));
+        const bool pipe = uni && !cw_model && h->uw_pipe != 0 && (h->uw_pipe == 2 || (left <= static_cast<uint32_t>(h->n_cu) * 4u && text_bytes / n >= 4096u));
         if (pipe) snprintf(ws->slot_name[kSlotLong], sizeof(ws->slot_name[kSlotLong]), "UniLongPipeKernel");
         if (pipe) HIP_OR_RETURN(h, LaunchUniLongPipe(la, UniWaveRow(h->tables.max_piece_len), static_cast<int>(left < static_cast<uint32_t>(h->n_cu) * 8u ? left : static_cast<uint32_t>(h->n_cu) * 8u), stream));
+        else if (cw_model) HIP_OR_RETURN(h, LaunchCharWordLong(h->model.model_type == kWord, la, static_cast<int>(g), stream));
         else if (uni) HIP_OR_RETURN(h, LaunchUniLong(la, UniWaveRow(h->tables.max_piece_len), static_cast<int>(g), stream));
         else HIP_OR_RETURN(h, LaunchBpeLong(la, static_cast<int>(g), stream));
         HIP_OR_RETURN(h, record(kSlotLong, 1));
@@ -1003,8 +1019,12 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     // the classes beyond the main streaming launch's (16 KiB) always; the classes between 4 and 16 KiB when they are
     // most of the batch (a batch OF documents: one lane per document would leave the chip idle), not when they are a
     // tail of a batch of sentences (there they hide behind the main launch's other tiles).
-    const bool uni_wave = !is_bpe && !spans && h->tables.max_prefixes >= 1 &&
-                          h->tables.max_piece_len <= static_cast<int>(kUwMaxPiece) && !h->no_uni_wave;
+    // (word models and character models without USER_DEFINED pieces: their own wave-cooperative form, kernels_charwave.h,
+    // through the same routing -- long_launch picks the kernel by the model type; it records token begins, so spans too)
+    const bool uni_wave = (cw_model && !h->no_uni_wave && (h->model.model_type == kWord || !uds)) ||
+                          (h->model.model_type == kUnigram && !spans && h->tables.max_prefixes >= 1 &&
+                           h->tables.max_piece_len <= static_cast<int>(kUwMaxPiece) && !h->no_uni_wave);
+    const bool cw_wave = cw_model && uni_wave;
     bool uni_class[kMaxClasses] = {false};
     if (uni_wave) {
       uint64_t vol_staged = 0, vol_mid = 0;
@@ -1364,7 +1384,11 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       if (forked && tail_total > 0) FORKED_HIP_OR_RETURN(hipStreamSynchronize(ws->stream2));
       FORKED_OR_RETURN(general_pass(left_lists[left_at], ws->d_ctrl->left_counts[left_at], known, true));
     } else {
+      // (general_pass consumes the counts of the classes it gives to a wave-cooperative form; the spans form's align
+      // launches below visit every class of the classify lists: they keep a copy)
+      for (int c = 0; c < ncls; ++c) align_known[c] = known[c];
       FORKED_OR_RETURN(general_pass(class_lists, ws->d_ctrl->list_counts, known, false));
+      if (cw_model) for (int c = 0; c < ncls; ++c) known[c] = align_known[c];
     }
     // ---- join ----
     if (forked) FORKED_HIP_OR_RETURN(hipStreamWaitEvent(stream, ws->ev_join, 0));
@@ -1379,7 +1403,9 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     if (ws->h_ctrl->side.over_count) {             // sentences that fit no column of their launch: exact capacities
       uint32_t counts[kMaxClasses] = {0};
       counts[kMaxClasses - 1] = ws->h_ctrl->side.over_count;
-      if (int rc = stream_launch(kSlotExact, 2, 0, 0, counts, true, ws->h_ctrl->side.over_max_raw); rc != kOk) return rc;
+      // (word / char models with a wave-cooperative form: a sentence that fits no text column goes there, a wavefront each)
+      if (cw_wave) { if (int rc = long_launch(over_list, &ws->d_ctrl->side.over_count, ws->h_ctrl->side.over_count, true); rc != kOk) return rc; }
+      else if (int rc = stream_launch(kSlotExact, 2, 0, 0, counts, true, ws->h_ctrl->side.over_max_raw); rc != kOk) return rc;
       extra = true;
       if (is_bpe) {                                // it may have added to the long list
         HIP_OR_RETURN(h, hipMemcpyAsync(&ws->h_ctrl->side, &ws->d_ctrl->side, sizeof(SideLists), hipMemcpyDeviceToHost, stream));
@@ -2126,7 +2152,7 @@ int EncodeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, u
   // offsets are used as given: the kernels address text + offs[i], so rebase the text pointer instead (they read
   // aligned 16-byte blocks of the absolute address: nothing before the staging buffer, at most 15 bytes of its slack after)
   const uint8_t *d_text = ws->d_text.p - base;
-  uint64_t cap = text_bytes / 2 + 4 * n + 64, total = 0, failed = 0;
+  uint64_t cap = IdsGuess(h, text_bytes, n), total = 0, failed = 0;
   int rc = kOk;
   for (int attempt = 0; attempt < 2; ++attempt) {
     e = ws->d_ids.Reserve(cap);
@@ -2283,7 +2309,7 @@ int EncodeBatchPipelined(spmx_handle *const *hs, int n_h, const char *text, cons
   const uint64_t text_bytes = cbeg[n_chunks];
   uint64_t max_bytes = 0;                                        // the largest chunk: what every worker's workspace is sized for
   for (uint64_t k = 0; k < n_chunks; ++k) if (cbeg[k + 1] - cbeg[k] > max_bytes) max_bytes = cbeg[k + 1] - cbeg[k];
-  uint64_t cap = text_bytes / 2 + 4 * n + 64;                    // ids the output array holds (more: the plain path takes over)
+  uint64_t cap = IdsGuess(h, text_bytes, n);                     // ids the output array holds (more: the plain path takes over)
   int32_t *out_ids = static_cast<int32_t *>(g_pinned.Get(cap * sizeof(int32_t)));
   uint64_t *out_offs = static_cast<uint64_t *>(g_pinned.Get((n + 1) * sizeof(uint64_t)));
   uint8_t *out_st = status ? static_cast<uint8_t *>(g_pinned.Get(n)) : nullptr;
@@ -2318,7 +2344,7 @@ int EncodeBatchPipelined(spmx_handle *const *hs, int n_h, const char *text, cons
       HIP_OR_RETURN(h, ws->d_offs.Reserve(max_cnt + 1));
       HIP_OR_RETURN(h, ws->d_id_offs.Reserve(max_cnt + 1));
       HIP_OR_RETURN(h, ws->d_sent_status.Reserve(max_cnt));
-      HIP_OR_RETURN(h, ws->d_ids.Reserve(max_bytes / 2 + 4 * max_cnt + 64));
+      HIP_OR_RETURN(h, ws->d_ids.Reserve(IdsGuess(h, max_bytes, max_cnt)));
       for (uint64_t k = static_cast<uint64_t>(w); k < n_chunks; k += static_cast<uint64_t>(T)) {
         const uint64_t s0 = k * chunk, s1 = (k + 1) * chunk < n ? (k + 1) * chunk : n, cnt = s1 - s0;
         const uint64_t bytes = cbeg[k + 1] - cbeg[k];
@@ -2337,7 +2363,7 @@ int EncodeBatchPipelined(spmx_handle *const *hs, int n_h, const char *text, cons
         }
         if (bytes) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_text.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
         HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, ws->h_offs.p, (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        uint64_t want = bytes / 2 + 4 * cnt + 64, total = 0, failed = 0;
+        uint64_t want = IdsGuess(h, bytes, cnt), total = 0, failed = 0;
         int r = kOk;
         for (int attempt = 0; attempt < 2; ++attempt) {
           HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
@@ -2863,6 +2889,8 @@ int SampleEncodeImpl(spmx_handle *h, const char *text, const uint64_t *offsets, 
     *ids = nullptr; *id_offsets = nullptr;
     if (spans) { *begin = nullptr; *end = nullptr; *nbegin = nullptr; *nend = nullptr; }
     if (nbest_size > 512) return Fail(h, kInternal, "nbest_size must be nbest_size <= 512");   // sentencepiece_processor.cc:684
+    if (h->model.model_type == kWord || h->model.model_type == kChar)       // neither IsNBestEncodeAvailable() nor IsSampleEncodeAvailable()
+      return Fail(h, kInternal, "SampleEncode is not available for the current model.");   // sentencepiece_processor.cc:689-691
     if (h->model.model_type == kBpe) {
       // !IsNBestEncodeAvailable(): every nbest_size goes to bpe::Model::SampleEncode(normalized, alpha) (:688-693),
       // BPE-dropout with merge-skip probability alpha; alpha <= 0 is the plain merge order (bpe_model.cc:131-156)
@@ -3380,7 +3408,7 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
           uint64_t n_lines = 0, text_bytes = 0;
           int r = spmx_split_lines_device(h, d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &n_lines, &text_bytes);
           if (r != kOk) return r;
-          uint64_t want = text_bytes / 2 + 4 * n_lines + 64, total = 0;
+          uint64_t want = IdsGuess(h, text_bytes, n_lines), total = 0;
           for (int attempt = 0; attempt < 2; ++attempt) {
             HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
             r = EncodeDevice(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
@@ -3496,3 +3524,8 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
 }
 
 }  // extern "C"
+
+#ifdef SPMX_WAVE_API
+// (the test suite's wavefront emulator builds this file against its own launchers: tests/emu)
+#include "../../tests/emu/emu_launch_charword.h"
+#endif

@@ -60,6 +60,8 @@ constexpr uint32_t kSpByte = 0xFFu;
 constexpr uint32_t kPtUnused = 1u << 31;
 constexpr uint32_t kPtUserDefined = 1u << 30;
 constexpr uint32_t kPtIdMask = (1u << 30) - 1;
+// word / char models (kernels_charword.h): the id field of a unit whose string is a CONTROL piece -- such a cut fails its sentence
+constexpr uint32_t kPtControlCut = kPtIdMask;
 
 constexpr uint32_t kSymNone = 0xFFFFFFFFu;
 // sym_final word: final id | flags
@@ -100,13 +102,16 @@ struct SpmxDev {
   // rule's replacement over its key, U+FFFD for one malformed byte, a space escaped to U+2581), tables.cc
   uint32_t expand_max;
   // ---- unigram (reference: src/unigram_model.cc:889-1020) ----
-  const U4 *ptrie;        // piece trie with inline id / flags / score
+  const U4 *ptrie;        // piece trie with inline id / flags / score (word / char models: PieceToId's exact-match trie
+                          // over the pieces map and then the reserved map, no scores -- kernels_charword.h)
   const uint8_t *plen;    // per id: the piece's byte length in the device form of the text (the short back-pointer form)
   // first-CHARACTER table (null: none): by code point U+0080 .. U+FFFF the unit of ptrie reached after the character's two
   // or three UTF-8 bytes, its label byte replaced by the character's byte length (0x100 clear: no piece starts with the
   // character).  Built for vocabularies with many pieces in multi-byte scripts when no piece ends inside a character
   // (tables.cc BuildFirstCharTable); the streaming kernel starts a walk there instead of spelling the character
   // (kernels_stream.h unigram_stream_lane).
+  // Character models without USER_DEFINED pieces have it too (kernels_charword.h): the unit behind a character is that
+  // character's PieceToId.
   const U4 *cfirst;
   float unk_score;        // min_score - 10.0f
   float max_score;
@@ -170,7 +175,7 @@ struct SpmxDev {
   const float *pscore;
   uint32_t umemo16_mask, umemo_mask, uall_mask, uall_perfect;
   uint32_t n_pieces;      // symbols below this are piece ids (their own final id); the rest are extra characters
-  int32_t model_type;     // 1 unigram, 2 bpe
+  int32_t model_type;     // 1 unigram, 2 bpe, 3 word, 4 char (the ModelType of csrc/model.h)
 };
 
 // ptrie unit word w: 32-bit summary of the node's child labels, bit ChildBit(c) set for every child byte c.

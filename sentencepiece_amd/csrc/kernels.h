@@ -1367,6 +1367,7 @@ SPMX_DEVICE void compact_big_block(const CompactArgs &a) {
 }  // namespace spmx
 
 #include "kernels_bpe_stream.h"
+#include "kernels_charword.h"
 #include "kernels_stream.h"
 #include "kernels_word.h"
 #include "kernels_wordwave.h"
@@ -1377,6 +1378,7 @@ SPMX_DEVICE void compact_big_block(const CompactArgs &a) {
 #include "kernels_nbest.h"
 #include "kernels_long.h"
 #include "kernels_uniwave.h"
+#include "kernels_charwave.h"
 #include "kernels_gather.h"
 
 #endif

@@ -40,6 +40,16 @@ __global__ __launch_bounds__(1024) void EncodeBpeStreamKernel(EncodeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   encode_stream_block<2, 0, false>(a, smem);
 }
+// word and character models (kernels_charword.h): the same persistent launch with their lane functions
+__global__ __launch_bounds__(1024) void EncodeWordModelStreamKernel(EncodeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  encode_stream_block<3, 0, false>(a, smem);
+}
+template <bool UDS>
+__global__ __launch_bounds__(1024) void EncodeCharStreamKernel(EncodeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  encode_stream_block<4, 0, UDS>(a, smem);
+}
 __global__ __launch_bounds__(1024) void EncodeWordKernel(EncodeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   encode_word_block<false, kWmPlain>(a, smem);
@@ -183,6 +193,28 @@ hipError_t LaunchEncodeStream(int model_type, bool uds, const EncodeArgs &a, int
   EncodeFn fn = model_type == 2 ? EncodeBpeStreamKernel : a.bp_short ? (a.ring == 16 ? EncodeStreamShortKernel<16> : EncodeStreamShortKernel<0>)
                                 : (a.ring == 16 ? (uds ? EncodeStreamKernel<16, true> : EncodeStreamKernel<16, false>)
                                                 : (uds ? EncodeStreamKernel<0, true> : EncodeStreamKernel<0, false>));
+  if (lds_bytes > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(lds_bytes));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * waves), lds_bytes, stream, a);
+  return hipGetLastError();
+}
+
+template <bool WORD>
+__global__ __launch_bounds__(64) void CharWordWaveKernel(LongArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kCwWaveLdsBytes];
+  charword_long_block<WORD>(a, smem);
+}
+hipError_t LaunchCharWordLong(bool word, const LongArgs &a, int grid, hipStream_t stream) {
+  if (word) hipLaunchKernelGGL(CharWordWaveKernel<true>, dim3(grid), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(CharWordWaveKernel<false>, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t LaunchEncodeCharWord(int model_type, bool uds, const EncodeArgs &a, int grid, int waves, uint32_t lds_bytes, hipStream_t stream) {
+  EncodeFn fn = model_type == 3 ? EncodeWordModelStreamKernel : (uds ? EncodeCharStreamKernel<true> : EncodeCharStreamKernel<false>);
   if (lds_bytes > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds_bytes));

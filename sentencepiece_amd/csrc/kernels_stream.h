@@ -126,10 +126,11 @@ struct StreamLds {
 // bytes of the text window: a power of two that holds the longest piece (< ring), the two bytes looked at beyond it
 // and the dword in flight
 SPMX_HD inline uint32_t StreamWindow(uint32_t ring) { uint32_t w = 32; while (w < ring + 6u) w <<= 1; return w; }
-// model: 1 unigram, 2 BPE
-// bpsz: bytes of a back-pointer entry (4; 2 in the short form, see BpShort)
+// model: 1 unigram, 2 BPE, 3 word / 4 char (kernels_charword.h: no working set in LDS beyond the normalizers' raw windows)
+// bpsz: bytes of a back-pointer entry (4; 2 in the short form, see BpShort; 0 for word / char models: no back-pointers)
 SPMX_HD inline uint32_t StreamPrivateBytes(int model, uint32_t ring, uint32_t bpsz = 4u) {
-  uint32_t work = model == 2 ? BpeWordLdsBytes() + 64u * (kBpeWindow + 4u)
+  uint32_t work = model >= 3 ? 0u
+                : model == 2 ? BpeWordLdsBytes() + 64u * (kBpeWindow + 4u)
                              : 64u * ring * (4u + bpsz) + 64u * (StreamWindow(ring) + 4u) + 64u * 8u * bpsz;
   if (work < 64u * kRawWinBytes) work = 64u * kRawWinBytes;
   return ((work + 15u) & ~15u) + 256u;                 // + the backlog
@@ -484,14 +485,14 @@ SPMX_DEVICE void append_lanes(uint64_t m, bool mine, uint32_t sid, uint32_t *lis
   if (mine) list[base + static_cast<uint32_t>(wv::popc64(m & ((1ull << lane) - 1ull)))] = sid;
 }
 
-// Persistent body of the streaming kernels.  MODEL: 1 unigram, 2 BPE (word-wise models only).  RING: see
-// unigram_stream_lane (0 = a.ring).  UDS: the model may have USER_DEFINED pieces.
+// Persistent body of the streaming kernels.  MODEL: 1 unigram, 2 BPE (word-wise models only), 3 word, 4 char
+// (kernels_charword.h).  RING: see unigram_stream_lane (0 = a.ring).  UDS: the model may have USER_DEFINED pieces.
 // SPLIT_ONLY: every tile of the launch takes the split form (kernels_matchfold.h; EncodeSplitKernel): the lane-per-sentence
 // normalizers and search are not even compiled in, and the wavefront's LDS slice is the split form's own (12 per CU).
 template <int MODEL, int RING, bool UDS, typename BP = BpWord, bool SPLIT_ONLY = false>
 SPMX_DEVICE void encode_stream_block(const EncodeArgs &a, unsigned char *smem) {
   typedef typename BP::T BT;
-  constexpr uint32_t kBpSz = sizeof(BT);
+  constexpr uint32_t kBpSz = MODEL >= 3 ? 0u : sizeof(BT);     // (word / char models keep no back-pointers: text columns only)
   const int lane = wv::lane();
   const SpmxDev &d = a.dev;
   const uint32_t ring = RING ? static_cast<uint32_t>(RING) : a.ring;
@@ -503,9 +504,9 @@ SPMX_DEVICE void encode_stream_block(const EncodeArgs &a, unsigned char *smem) {
   uint8_t *my_win = T.win + static_cast<uint32_t>(lane) * (W + 4u);
   uint8_t *my_raw = T.rawwin + static_cast<uint32_t>(lane) * kRawWinBytes;
   {   // shared read-only tables; every wave writes all of both (same values): no workgroup barrier
-    const uint32_t root = MODEL == 1 ? d.ptrie[0].x >> kDatBaseShiftDev : 0u;
+    const uint32_t root = MODEL != 2 ? d.ptrie[0].x >> kDatBaseShiftDev : 0u;
     for (uint32_t cb = static_cast<uint32_t>(lane); cb < 256u; cb += 64u) {
-      if (MODEL == 1) {
+      if (MODEL != 2) {
         U4 r = d.ptrie[root ^ cb];
         if ((r.x & 0x1FFu) != (0x100u | cb)) r = U4{0, 0, 0, 0};
         // the label byte is redundant here (it is the index): it carries the byte length of a character that
@@ -702,7 +703,8 @@ SPMX_DEVICE void encode_stream_block(const EncodeArgs &a, unsigned char *smem) {
     const bool overflow = base + static_cast<unsigned long long>(total + 3) > a.arena_cap;
     if (overflow && lane == 0) wv::atomic_or(a.status, kStArenaOverflow);
     base = (base + 3ull) & ~3ull;
-    const int at = excl + d.n_prefix + ((d.flags & kNfReverse) ? 0 : cap);
+    // (word / char models fill the slot the other way round: from its start, from its end when reversing)
+    const int at = excl + d.n_prefix + (((d.flags & kNfReverse) != 0) == (MODEL >= 3) ? cap : 0);
     const int shift = (4 - (at & 3)) & 3;
     int32_t *slot = a.arena + base + static_cast<unsigned long long>(excl + shift) + d.n_prefix;
     int32_t *tslot = a.arena_tb ? a.arena_tb + base + static_cast<unsigned long long>(excl + shift) + d.n_prefix : nullptr;
@@ -731,6 +733,12 @@ SPMX_DEVICE void encode_stream_block(const EncodeArgs &a, unsigned char *smem) {
         n = emit_stream_lane<BP>(d, gt, gb, my_nlen, slot, tslot, cap, reinterpret_cast<int32_t *>(my_rs), mine);
         at_end = (d.flags & kNfReverse) == 0;
       }
+    } else if (MODEL >= 3) {
+      // ---- cut by cut in text order (kernels_charword.h): the slot is filled from its start (end when reversing) ----
+      if (MODEL == 3) n = word_stream_lane(d, gt, my_nlen, slot, tslot, cap, T.roottab, mine && !overflow);
+      else n = char_stream_lane<UDS>(d, gt, my_nlen, slot, tslot, cap, T.roottab, mine && !overflow);
+      c2 = wv::clock();
+      at_end = (d.flags & kNfReverse) != 0;
     } else {
       // ---- word by word, ids written as the words complete: the slot is filled from its start (end when reversing) ----
       n = bpe_stream_lane(d, gt, my_nlen, slot, tslot, cap, T.bw, T.asym, T.bwin + static_cast<uint32_t>(lane) * (kBpeWindow + 4u),

@@ -35,6 +35,12 @@ inline uint32_t ScoreRing(int max_piece_len) {
 // One streaming launch (kernels_stream.h): model_type 1 unigram / 2 BPE; uds: the model has USER_DEFINED pieces
 hipError_t LaunchEncodeStream(int model_type, bool uds, const EncodeArgs &a, int grid, int waves,
                               uint32_t lds_bytes, hipStream_t stream);
+// the same launch for word (model_type 3) and character (4) models (kernels_charword.h)
+hipError_t LaunchEncodeCharWord(int model_type, bool uds, const EncodeArgs &a, int grid, int waves, uint32_t lds_bytes,
+                                hipStream_t stream);
+// their wave-cooperative form (kernels_charwave.h): a sentence per 64-thread workgroup over a device-side list, slices from
+// the long form's pool; word: a word model, else a character model without USER_DEFINED pieces
+hipError_t LaunchCharWordLong(bool word, const LongArgs &a, int grid, hipStream_t stream);
 // the same launch with EVERY tile in the split form (kernels_matchfold.h): unigram, no user-defined pieces
 hipError_t LaunchEncodeSplit(const EncodeArgs &a, int grid, int waves, uint32_t lds_bytes, hipStream_t stream);
 // The word kernel (kernels_word.h): unigram models with kNfUniWordwise

@@ -125,13 +125,30 @@ static float UwFloatLimit(const ModelData &m, float unk_score) {
   return limit > 0.0 ? static_cast<float>(limit * 0.999) : 0.0f;
 }
 
+// child-label summaries of a piece trie (dev.h ChildBit): a unit at index j with label c is the child of the node whose
+// base is j ^ c; bases are unique, so map base -> node unit first
+static void ChildSummaries(const DatTrie &d, std::vector<U4> *ptrie) {
+  std::vector<uint32_t> owner(d.w0.size(), 0xFFFFFFFFu);   // base -> unit that owns it
+  for (size_t i = 0; i < d.w0.size(); ++i)
+    if (i == 0 || (d.w0[i] & kDatOccupied)) {
+      const uint32_t base = d.w0[i] >> kDatBaseShift;
+      if (base < owner.size() && (i == 0 || base != 0)) owner[base] = static_cast<uint32_t>(i);
+    }
+  for (size_t j = 1; j < d.w0.size(); ++j) {
+    if (!(d.w0[j] & kDatOccupied)) continue;
+    const uint32_t c = d.w0[j] & 0xFFu;
+    const uint32_t base = static_cast<uint32_t>(j) ^ c;
+    if (base < owner.size() && owner[base] != 0xFFFFFFFFu) (*ptrie)[owner[base]].w |= 1u << ChildBit(c);
+  }
+}
+
 Status CompileTables(const ModelData &m, HostTables *t) {
   std::string err;
   SpmxDev &sc = t->scalars;
   sc = SpmxDev{};
   sc.model_type = m.model_type;
-  if (!m.normalizer_only && m.model_type != kUnigram && m.model_type != kBpe)
-    return Status::Error(kUnimplemented, "only unigram and bpe models are on the device path");
+  if (!m.normalizer_only && m.model_type != kUnigram && m.model_type != kBpe && m.model_type != kWord && m.model_type != kChar)
+    return Status::Error(kUnimplemented, "unknown model_type on the device path");
   if (m.pieces.size() >= (1u << 30)) return Status::Error(kResourceExhausted, "vocabulary too large");
   uint32_t flags = 0;
   if (m.add_dummy_prefix) flags |= kNfAddDummyPrefix;
@@ -422,21 +439,37 @@ Status CompileTables(const ModelData &m, HostTables *t) {
       }
       t->ptrie[i] = u;
     }
-    // child-label summaries (dev.h ChildBit): a unit at index j with label c is the child of the node whose
-    // base is j ^ c; bases are unique, so map base -> node unit first
-    {
-      std::vector<uint32_t> owner(d.w0.size(), 0xFFFFFFFFu);   // base -> unit that owns it
-      for (size_t i = 0; i < d.w0.size(); ++i)
-        if (i == 0 || (d.w0[i] & kDatOccupied)) {
-          const uint32_t base = d.w0[i] >> kDatBaseShift;
-          if (base < owner.size() && (i == 0 || base != 0)) owner[base] = static_cast<uint32_t>(i);
+    ChildSummaries(d, &t->ptrie);
+  } else if (m.model_type == kWord || m.model_type == kChar) {
+    // PieceToId (src/model_interface.cc:51-61) as ONE exact-match trie: the pieces map (NORMAL, USER_DEFINED, UNUSED), then
+    // the reserved map (CONTROL, UNKNOWN, BYTE) for the strings the pieces map lacks; every other string is unk_id.  The
+    // same 16-byte units as the unigram trie, walked a byte at a time (kernels_charword.h): y = id, plus kPtUserDefined
+    // for the pieces the character model's PrefixMatcher cuts out whole (the types at load, src/model_interface.cc:
+    // InitializePieces); kPtControlCut for a CONTROL piece.  No scores, no length limit: nothing here is indexed by a
+    // piece's length.
+    std::map<std::string, uint32_t> all;
+    for (const auto &kv : m.pieces_map) all.emplace(compress ? CompressSp(kv.first) : kv.first, static_cast<uint32_t>(kv.second));
+    for (const auto &kv : m.reserved_map) all.emplace(compress ? CompressSp(kv.first) : kv.first, static_cast<uint32_t>(kv.second));
+    all.erase(std::string());                        // (a cut is never empty)
+    std::vector<std::pair<std::string, uint32_t>> keys(all.begin(), all.end());
+    if (keys.empty()) {
+      t->ptrie.assign(256, U4{0, 0, 0, 0});
+    } else {
+      DatTrie d;
+      if (!BuildDat(keys, &d, &err)) return Status::Error(kInternal, "piece trie: " + err);
+      t->ptrie.resize(d.w0.size());
+      for (size_t i = 0; i < d.w0.size(); ++i) {
+        U4 u{d.w0[i], 0, 0, 0};
+        if (d.value[i] != 0xFFFFFFFFu) {
+          const PieceRec &pr = m.pieces[d.value[i]];
+          // a cut that is a CONTROL piece's string consumes no text in PopulateSentencePieceText (:561-567): the reference
+          // fails the sentence with "all normalized characters are not consumed." (:628) -- kPtControlCut instead of the id
+          u.y = (pr.load_type == kControl || pr.type == kControl) ? kPtControlCut
+              : d.value[i] | (m.model_type == kChar && pr.load_type == kUserDefined ? kPtUserDefined : 0u);
         }
-      for (size_t j = 1; j < d.w0.size(); ++j) {
-        if (!(d.w0[j] & kDatOccupied)) continue;
-        const uint32_t c = d.w0[j] & 0xFFu;
-        const uint32_t base = static_cast<uint32_t>(j) ^ c;
-        if (base < owner.size() && owner[base] != 0xFFFFFFFFu) t->ptrie[owner[base]].w |= 1u << ChildBit(c);
+        t->ptrie[i] = u;
       }
+      ChildSummaries(d, &t->ptrie);
     }
   } else {
     t->ptrie.assign(256, U4{0, 0, 0, 0});
@@ -653,7 +686,10 @@ Status CompileTables(const ModelData &m, HostTables *t) {
 void BuildFirstCharTable(const ModelData &m, HostTables *t) {
   t->cfirst.clear();
   t->scalars.cfirst = nullptr;
-  if (m.model_type != kUnigram || t->ptrie.empty() || getenv("SPMX_NO_CFIRST")) return;
+  // (character models without USER_DEFINED pieces too: there the unit behind a character IS the character's PieceToId, one
+  // load instead of a chain of two or three probes -- kernels_charword.h char_stream_lane)
+  const bool char_direct = m.model_type == kChar && !(t->scalars.flags & kNfHasUserDefined);
+  if ((m.model_type != kUnigram && !char_direct) || t->ptrie.empty() || getenv("SPMX_NO_CFIRST")) return;
   size_t multi = 0;
   const bool one_byte_sp = (t->scalars.flags & kNfCompressSp) != 0;      // (the space symbol is then the byte 0xFF in the trie's keys)
   for (const auto &kv : m.pieces_map) {
@@ -661,7 +697,7 @@ void BuildFirstCharTable(const ModelData &m, HostTables *t) {
     if (one_byte_sp && kv.first.compare(0, 3, kSpaceSymbol) == 0) continue;
     if (c0 >= 0xC2 && c0 < 0xF0) ++multi;
   }
-  if (multi < 1024) return;                              // (an ASCII vocabulary: the table would only cost cache)
+  if (multi < (char_direct ? 16u : 1024u)) return;       // (an ASCII vocabulary: the table would only cost cache)
   const uint32_t root = t->ptrie[0].x >> kDatBaseShiftDev;
   std::vector<U4> tab(65536, U4{1, 0, 0, 0});
   for (uint32_t cp = 0x80; cp < 0x10000; ++cp) {

@@ -271,6 +271,7 @@ class SentencePieceProcessor:
         return buf.raw[:n].decode("utf-8", "replace")
 
     def model_type(self):
+        """trainer_spec.model_type of the loaded model: 1 unigram, 2 bpe, 3 word, 4 char."""
         self._need()
         return self._lib.spmx_model_type(self._h)
 
@@ -473,6 +474,12 @@ class SentencePieceProcessor:
             self._lib.spmx_free(p_off)
         return ids, io
 
+    def _ids_guess(self, text_bytes, n):
+        """First guess at the ids of a batch (a too-small array is allocated again with the exact count): a character
+        model gives about one id per byte (and a word model with byte fallback can), the others fewer than one per two."""
+        per_byte = self.model_type() == 4 or (self.model_type() == 3 and self.IsByte(self.PieceToId("<0x00>")))
+        return text_bytes + 6 * n + 64 if per_byte else text_bytes // 2 + 4 * n + 64
+
     def EncodeDevice(self, d_text, d_offsets, d_ids=None, d_id_offsets=None, stream=None,
                      add_bos=False, add_eos=False, reverse=False):
         """Device-resident form over torch tensors on this processor's GPU.
@@ -488,7 +495,7 @@ class SentencePieceProcessor:
         if d_id_offsets is None:
             d_id_offsets = torch.empty(n + 1, dtype=torch.int64, device=d_text.device)
         if d_ids is None:
-            d_ids = torch.empty(d_text.numel() // 2 + 4 * n + 64, dtype=torch.int32, device=d_text.device)
+            d_ids = torch.empty(self._ids_guess(d_text.numel(), n), dtype=torch.int32, device=d_text.device)
         if stream is None:
             stream = torch.cuda.current_stream(d_text.device).cuda_stream if d_text.is_cuda else 0
         total = C.c_uint64(0)
@@ -548,7 +555,7 @@ class SentencePieceProcessor:
         n = d_offsets.numel() - 1
         dev = d_text.device
         d_id_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        cap = d_text.numel() // 2 + 4 * n + 64
+        cap = self._ids_guess(d_text.numel(), n)
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
         total = C.c_uint64(0)
