@@ -1212,6 +1212,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
         EncodeArgs wa = a;
         const bool wform = !dp && ((mode == 2 ? h->word_form & 2 : h->word_form & 1) != 0);   // word per lane
         int waves = dp ? 8 : wform ? h->wordwave_waves : h->word_waves;
+        if (wform && mode == 2 && waves > static_cast<int>(kWwAgainMaxWaves)) waves = static_cast<int>(kWwAgainMaxWaves);   // (the second round's launch bound: three wavefronts per SIMD, its pipeline in registers)
         while (wform && waves > 1 && WordWaveLdsBytes(static_cast<uint32_t>(waves)) > 160u * 1024u) --waves;   // (a CU's LDS: an A/B build with a larger hot table)
         uint64_t total = 0;
         for (int c = 0; c < ncls; ++c) total += known[c];

@@ -73,8 +73,11 @@ __global__ __launch_bounds__(1024) void EncodeWordWaveCollectKernel(EncodeArgs a
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   encode_wordwave_block<kWmCollect, H16>(a, smem);
 }
+// The second round carries the call-local memo's slot per word and stage as well: 150 vector registers.  At most
+// kWwAgainMaxWaves wavefronts a workgroup (three per SIMD, 168 registers) keep all of it in registers -- under the 128 of
+// a 1024-thread bound the compiler put part of the pipeline's stages into scratch.
 template <bool H16>
-__global__ __launch_bounds__(1024) void EncodeWordWaveAgainKernel(EncodeArgs a) {
+__global__ __launch_bounds__(64 * kWwAgainMaxWaves) void EncodeWordWaveAgainKernel(EncodeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   encode_wordwave_block<kWmDyn, H16>(a, smem);
 }
@@ -253,6 +256,7 @@ hipError_t LaunchEncodeWordWave(int mode, const EncodeArgs &a, int grid, int wav
                                        static_cast<int>(lds_bytes));
     if (e != hipSuccess) return e;
   }
+  if (mode == 2 && waves > static_cast<int>(kWwAgainMaxWaves)) return hipErrorInvalidValue;   // (its launch bound; api.cc shapes the launch so)
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * waves), lds_bytes, stream, a);
   return hipGetLastError();
 }

@@ -52,6 +52,7 @@ constexpr uint32_t kWwRecs = 128u + 512u;           // the word queue: what the 
 constexpr uint32_t kWwMaxLen = 65536u;              // longer sentences are not taken (record positions have 26 bits)
 constexpr uint32_t kWwPerWave = kWwRing + kWwRingPad + kWwMaskBytes + kWwRecs * 4u + 64u * 16u + 64u * 8u + 5u * 64u * 4u;
 static_assert(kWwPerWave % 16u == 0u, "per-wave LDS blocks keep 16-byte alignment");
+constexpr uint32_t kWwAgainMaxWaves = 12u;          // wavefronts per workgroup of the second round (its launch bound, kernels.hip)
 constexpr uint32_t kWwAgain = 1u, kWwGone = 2u;     // per-sentence status bits
 constexpr uint32_t kWwKeyMaskBytes = 640u;          // 18 rows {key mask, padding under the mask's zeros} of 32 bytes (+ slack)
 // + the LDS table of the likeliest words (kWordHotSlots entries of uhot2), the displacements of uall's perfect hash.
@@ -75,6 +76,34 @@ SPMX_DEVICE uint32_t space_mask16(const Q4 &v) {
 SPMX_DEVICE uint32_t key_dword_n(uint32_t text, int n) {
   const uint32_t m = n >= 4 ? 0xFFFFFFFFu : (n <= 0 ? 0u : (1u << (8 * n)) - 1u);
   return key_dword(text, m);
+}
+
+// (second round) a word whose first slot of the call-local memo holds another word: the slots behind it, until the word's
+// tag or a free slot (kernels_word.h kDynProbes).  A real call: rare, and its loop's loads stay apart from the pipeline's
+// registers.  hit: the slot holds the word's bytes and a usable entry {n | flags, bound, limit} {ids} {ids}.
+struct DynWalked { uint32_t hit, n, bound, lim; U4 ia, ib; };
+SPMX_DEVICE DynWalked dyn_walk(const unsigned long long *dyn_tag, const U4 *dyn_ent, uint32_t dyn_mask, uint32_t k0,
+                                    uint32_t k1, uint32_t k2, uint32_t k3, unsigned long long tag) {
+  DynWalked w{0u, 0u, 0u, 0u, U4{0, 0, 0, 0}, U4{0, 0, 0, 0}};
+  uint32_t sl = static_cast<uint32_t>(tag >> 32) & dyn_mask;
+#pragma unroll 1
+  for (uint32_t t = 1; t < kDynProbes; ++t) {
+    sl = (sl + 1u) & dyn_mask;
+    const unsigned long long g = dyn_tag[sl];
+    if (g == 0ull) break;
+    if (g != tag) continue;
+    const U4 d0 = dyn_ent[4u * sl], d1 = dyn_ent[4u * sl + 1u];
+    if (d0.x == k0 && d0.y == k1 && d0.z == k2 && d0.w == k3 && d1.x == 1u) {
+      w.hit = 1u; w.n = d1.y; w.bound = d1.z; w.lim = d1.w;
+      w.ia = dyn_ent[4u * sl + 2u];
+      w.ib = dyn_ent[4u * sl + 3u];
+      // (waited for here, on the rare path: a load still in flight at the join would make the common path wait as well)
+      wv::opaque(w.ia.x); wv::opaque(w.ia.y); wv::opaque(w.ia.z); wv::opaque(w.ia.w);
+      wv::opaque(w.ib.x); wv::opaque(w.ib.y); wv::opaque(w.ib.z); wv::opaque(w.ib.w);
+    }
+    break;                                             // (same hash, other bytes or an unusable word: a miss)
+  }
+  return w;
 }
 
 // what a batch of 64 words carries from one pipeline stage to the next (registers)
@@ -369,33 +398,30 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
         }
       }
       // ---- (second round) the call-local memo: words collected by the first round, segmented by word_resolve_block ----
+      // The slot the word's hash names came with the probe (stage A) and is tested straight from the stage's registers;
+      // another slot (a collision in the table) is walked to by dyn_walk -- rare: the table is sparse.  Nothing here is
+      // assigned both from the stage and from a load in a loop (that form made the compiler keep the stage in memory).
       bool hitd = false;
       uint32_t dn = 0;
       U4 dia{0, 0, 0, 0}, dib{0, 0, 0, 0};
       uint32_t dbound = 0u, dlim = 0u;
+      bool dib_late = false;                                         // the ids' second row is still to be asked for (below)
       if (MODE == kWmDyn && wv::any(probe & !hit32)) {
-        if (probe & !hit32) {
-          const unsigned long long tag = DynTag(k0, k1, k2, k3);
-          // the slot the word's hash names came with the probe (stage A); the ids are asked for now; another slot (a
-          // collision in the table) is walked to -- rare: the table is sparse
-          uint32_t sl = static_cast<uint32_t>(tag >> 32) & a.dyn_mask;
-          unsigned long long g = static_cast<unsigned long long>(S.tg_hi) << 32 | S.tg_lo;
-          U4 d0{S.d0x, S.d0y, S.d0z, S.d0w}, d1{S.d1x, S.d1y, S.d1z, S.d1w}, d2{S.d2x, S.d2y, S.d2z, S.d2w};
-          for (uint32_t t = 0; t < kDynProbes; ++t) {
-            if (g == 0ull) break;
-            if (g == tag) {
-              if (d0.x == k0 && d0.y == k1 && d0.z == k2 && d0.w == k3 && d1.x == 1u) {
-                hitd = true; dn = d1.y; dbound = d1.z; dlim = d1.w;
-                dia = d2;
-                // (the second half of the ids: only a word of more than four pieces -- or more than eight under kDynWide -- has it)
-                const uint32_t cn = d1.y & 0xFFu;
-                if ((d1.y & kDynWide) ? cn > 8u : cn > 4u) dib = a.dyn_ent[4u * sl + 3u];
-              }
-              break;                                     // (same hash, other bytes or an unusable word: a miss)
-            }
-            sl = (sl + 1u) & a.dyn_mask;
-            g = a.dyn_tag[sl];
-            d0 = a.dyn_ent[4u * sl]; d1 = a.dyn_ent[4u * sl + 1u]; d2 = a.dyn_ent[4u * sl + 2u];
+        const bool ask = probe & !hit32;
+        const unsigned long long tag = DynTag(k0, k1, k2, k3);
+        const unsigned long long g = static_cast<unsigned long long>(S.tg_hi) << 32 | S.tg_lo;
+        // (same hash, other bytes or an unusable word: a miss)
+        hitd = ask & (g == tag) & ((S.d0x == k0) & (S.d0y == k1)) & ((S.d0z == k2) & (S.d0w == k3)) & (S.d1x == 1u);
+        dn = S.d1y; dbound = S.d1z; dlim = S.d1w;
+        dia = U4{S.d2x, S.d2y, S.d2z, S.d2w};
+        dib_late = hitd;
+        const bool walkd = ask & (g != 0ull) & (g != tag);
+        if (wv::any(walkd)) {
+          if (walkd) {
+            const DynWalked w = dyn_walk(a.dyn_tag, a.dyn_ent, a.dyn_mask, k0, k1, k2, k3, tag);
+            hitd = w.hit != 0u;
+            dn = w.n; dbound = w.bound; dlim = w.lim;
+            dia = w.ia; dib = w.ib;
           }
         }
       }
@@ -520,6 +546,13 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
       }
       if (MODE == kWmDyn && wv::any(emit && hitd)) {
         const bool wide = (dn & kDynWide) != 0u;
+        // (the second half of the ids: only a word of more than four pieces -- or more than eight under kDynWide -- has it;
+        // asked for here, where it is used, and only when a word of the batch has one)
+        const bool more = emit && dib_late && (wide ? cntd > 8u : cntd > 4u);
+        if (wv::any(more)) {
+          if (more) dib = a.dyn_ent[4u * (static_cast<uint32_t>(DynTag(k0, k1, k2, k3) >> 32) & a.dyn_mask) + 3u];
+          wv::opaque(dib.x); wv::opaque(dib.y); wv::opaque(dib.z); wv::opaque(dib.w);   // (waited for on this rare path, not at the join)
+        }
         auto idc = [&](uint32_t t) __attribute__((always_inline)) -> uint32_t {   // piece t of the entry (t a constant after unrolling)
           const uint32_t di[8] = {dia.x, dia.y, dia.z, dia.w, dib.x, dib.y, dib.z, dib.w};
           if (wide) return t < 16u ? (di[(t >> 1) & 7u] >> (16u * (t & 1u))) & 0xFFFFu : 0u;
