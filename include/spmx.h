@@ -437,6 +437,40 @@ int spmx_split_lines_device(spmx_handle *h, const void *d_file, uint64_t bytes, 
 int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *format, uint64_t *n_sentences,
                      uint64_t *n_ids);
 
+/* ---- corpus file side of Decode ------------------------------------------
+ * The caller-side steps of the reference's spm_decode (src/spm_decode_main.cc: std::getline, StrSplit(line, " ") without
+ * empty tokens, atoi per token, Decode, WriteLine) on the device.
+ *
+ * Parser: a file image of id lines -> CSR ids.  Lines as in spmx_split_lines_device.  A token is a maximal run of bytes
+ * other than ' ' within a line; an empty line, or one of spaces, has no ids.  A token's value is glibc's atoi, bit for
+ * bit: leading \t \v \f \r, one sign, the digits up to the first other byte, strtol's saturation, the low 32 bits.
+ * d_file must be 16-byte aligned device memory, its allocation padded to 16 bytes.  d_ids takes ids_capacity entries,
+ * d_id_offsets offsets_capacity (n_lines + 1 are written).  Too small a capacity -> RESOURCE_EXHAUSTED (8) with the
+ * needed sizes in *n_lines (+ 1 offsets) and *n_ids.  bytes == 0: an empty CSR (d_id_offsets[0] = 0). */
+int spmx_parse_id_lines_device(spmx_handle *h, const void *d_file, uint64_t bytes, int32_t *d_ids, uint64_t ids_capacity,
+                               uint64_t *d_id_offsets, uint64_t offsets_capacity, void *stream, uint64_t *n_lines,
+                               uint64_t *n_ids);
+/* Joiner, the inverse of spmx_split_lines_device: packed text + n + 1 offsets (d_text_offsets[0] == 0, as the decode
+ * calls write them) -> a file image of d_text_offsets[n] + n bytes, every line followed by '\n'.  Too small a capacity
+ * (or d_out NULL) -> RESOURCE_EXHAUSTED (8) with the needed size in *out_bytes.  d_out may have any alignment. */
+int spmx_join_lines_device(spmx_handle *h, const void *d_text, const uint64_t *d_text_offsets, uint64_t n, void *d_out,
+                           uint64_t out_capacity, void *stream, uint64_t *out_bytes);
+
+/* ---- ids -> corpus file ---------------------------------------------------
+ * What the reference's `spm_decode --input_format=id < in > out` does, as one call and as the inverse of
+ * spmx_encode_file: the input is mmap'ed, cut at line ends into chunks of 64 MiB (SPMX_FILE_CHUNK, bytes, at least 4096:
+ * read at every call) and goes through up to 4 worker threads -- H2D, the parser, the decode kernels, the joiner, one
+ * D2H of the finished image, fwrite -- in order.  The decode extra options and a model's denormalizer apply.
+ * input_format "id": lines of decimal ids; "bin": in_path holds flat int32 ids and in_path + ".idx" the n + 1 uint64
+ * offsets (what spmx_encode_file's "bin" writes); "piece": lines of space-separated pieces, mapped with PieceToId on the
+ * host -- a token outside the vocabulary goes through as it is, or becomes the unknown piece under the decode option
+ * `unk`, as spmx_decode_batch_pieces documents.  NULL: "id".
+ * An id outside [0, GetPieceSize()) fails the call with OUT_OF_RANGE (11) "Invalid id: N": of several failing chunks
+ * the first one's status is returned, N being an invalid id of that chunk's first failing line.  What out_path holds
+ * after a failed call is unspecified.  A missing input: NOT_FOUND (5). */
+int spmx_decode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *input_format, uint64_t *n_lines,
+                     uint64_t *n_ids);
+
 /* ---- measurement --------------------------------------------------------
  * Per-kernel timing of the encode kernels of the LAST profiled encode call on the handle, measured with hipEvents
  * on the call's stream (enable first).  Arrays hold 7 entries ("kernel slots": 0 the streaming launch over the

@@ -3480,6 +3480,346 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
   });
 }
 
+/* ---- id lines -> CSR ids, packed text -> lines (kernels_idtext.h) ------------------------------------------------------ */
+namespace {
+// count pass -> two scans -> (host reads the totals and the last byte) -> write pass.  The needed sizes come back in
+// *n_lines / *n_ids also where the capacities do not suffice.
+int ParseIdLines(spmx_handle *h, Workspace *ws, const void *d_file, uint64_t bytes, int32_t *d_ids, uint64_t ids_capacity,
+                 uint64_t *d_id_offsets, uint64_t offsets_capacity, hipStream_t stream, uint64_t *n_lines, uint64_t *n_ids) {
+  *n_lines = 0;
+  *n_ids = 0;
+  if (bytes == 0) {
+    if (!d_id_offsets || offsets_capacity < 1) return Fail(h, kResourceExhausted, "ids_capacity / offsets_capacity is too small");
+    HIP_OR_RETURN(h, hipMemsetAsync(d_id_offsets, 0, sizeof(uint64_t), stream));
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+    return kOk;
+  }
+  const uint64_t chunks = (bytes + kSplitChunk - 1) / kSplitChunk;
+  if (chunks >= (1ull << 32) - 64) return Fail(h, kInvalidArgument, "file image too large for one call");
+  HIP_OR_RETURN(h, ws->d_counts.Reserve(2 * (chunks + 1)));
+  HIP_OR_RETURN(h, ws->d_chunk_base.Reserve(2 * (chunks + 1)));
+  HIP_OR_RETURN(h, ws->d_tile_sums.Reserve((chunks + kScanTile - 1) / kScanTile + 2));
+  ParseIdsArgs a{};
+  a.file = static_cast<const uint8_t *>(d_file); a.bytes = bytes;
+  a.nl_counts = ws->d_counts.p; a.tok_counts = ws->d_counts.p + chunks + 1;
+  a.nl_base = ws->d_chunk_base.p; a.tok_base = ws->d_chunk_base.p + chunks + 1;
+  a.ids = d_ids; a.id_offsets = d_id_offsets;
+  const uint64_t wide = static_cast<uint64_t>(h->n_cu) * 16;
+  const int grid = static_cast<int>(chunks < wide ? chunks : wide);
+  HIP_OR_RETURN(h, LaunchParseIdLines(false, a, grid, stream));
+  const uint32_t tiles = (static_cast<uint32_t>(chunks) + kScanTile - 1) / kScanTile;
+  const int scan_grid = static_cast<int>(tiles < static_cast<uint32_t>(h->n_cu * 8) ? tiles : h->n_cu * 8);
+  for (int which = 0; which < 2; ++which) {       // (the scans share tile_sums: they run one after the other on the stream)
+    ScanArgs sa{ws->d_counts.p + which * (chunks + 1), static_cast<uint32_t>(chunks), ws->d_tile_sums.p,
+                ws->d_chunk_base.p + which * (chunks + 1)};
+    HIP_OR_RETURN(h, LaunchScan(sa, scan_grid, stream));
+  }
+  uint64_t totals[2] = {0, 0};
+  uint8_t last = 0;
+  HIP_OR_RETURN(h, hipMemcpyAsync(&totals[0], a.nl_base + chunks, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_OR_RETURN(h, hipMemcpyAsync(&totals[1], a.tok_base + chunks, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_OR_RETURN(h, hipMemcpyAsync(&last, static_cast<const uint8_t *>(d_file) + bytes - 1, 1, hipMemcpyDeviceToHost, stream));
+  HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  const uint64_t lines = totals[0] + (last != 0x0A ? 1 : 0);      // std::getline: a last line without '\n' counts
+  *n_lines = lines;
+  *n_ids = totals[1];
+  if (!d_id_offsets || offsets_capacity < lines + 1 || (totals[1] && (!d_ids || ids_capacity < totals[1])))
+    return Fail(h, kResourceExhausted, "ids_capacity / offsets_capacity is too small");
+  HIP_OR_RETURN(h, LaunchParseIdLines(true, a, grid, stream));
+  HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  return kOk;
+}
+
+// known_text_bytes: text_offsets[n] where the caller has it already (no read-back then)
+int JoinLines(spmx_handle *h, const void *d_text, const uint64_t *d_text_offsets, uint64_t n, void *d_out, uint64_t out_capacity,
+              hipStream_t stream, uint64_t *out_bytes, const uint64_t *known_text_bytes = nullptr) {
+  *out_bytes = 0;
+  if (n == 0) return kOk;
+  if (!d_text_offsets) return Fail(h, kInvalidArgument, "null offsets");
+  uint64_t text_bytes = known_text_bytes ? *known_text_bytes : 0;
+  if (!known_text_bytes) {
+    HIP_OR_RETURN(h, hipMemcpyAsync(&text_bytes, d_text_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  }
+  const uint64_t total = text_bytes + n;
+  *out_bytes = total;
+  if (text_bytes && !d_text) return Fail(h, kInvalidArgument, "null text");
+  if (!d_out || out_capacity < total) return Fail(h, kResourceExhausted, "out_capacity is too small");
+  JoinLinesArgs a{};
+  a.text = static_cast<const uint8_t *>(d_text); a.offsets = d_text_offsets; a.n = n;
+  a.out = static_cast<uint8_t *>(d_out); a.out_bytes = total;
+  const uint64_t chunks = (total + 15 + kJoinChunk - 1) / kJoinChunk;
+  const uint64_t wide = static_cast<uint64_t>(h->n_cu) * 16;
+  HIP_OR_RETURN(h, LaunchJoinLines(a, static_cast<int>(chunks < wide ? chunks : wide), stream));
+  HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  return kOk;
+}
+}  // namespace
+
+int spmx_parse_id_lines_device(spmx_handle *h, const void *d_file, uint64_t bytes, int32_t *d_ids, uint64_t ids_capacity,
+                               uint64_t *d_id_offsets, uint64_t offsets_capacity, void *stream, uint64_t *n_lines,
+                               uint64_t *n_ids) {
+  if (!h) return kInvalidArgument;
+  if (n_lines) *n_lines = 0;
+  if (n_ids) *n_ids = 0;
+  if (!n_lines || !n_ids) return Fail(h, kInternal, "output container is null");
+  if (bytes && (!d_file || (reinterpret_cast<uintptr_t>(d_file) & 15u))) return Fail(h, kInvalidArgument, "d_file must be 16-byte aligned");
+  return Guard(h, [&]() -> int {
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    return ParseIdLines(h, L.ws.get(), d_file, bytes, d_ids, ids_capacity, d_id_offsets, offsets_capacity,
+                        static_cast<hipStream_t>(stream), n_lines, n_ids);
+  });
+}
+
+int spmx_join_lines_device(spmx_handle *h, const void *d_text, const uint64_t *d_text_offsets, uint64_t n, void *d_out,
+                           uint64_t out_capacity, void *stream, uint64_t *out_bytes) {
+  if (!h) return kInvalidArgument;
+  if (!out_bytes) return Fail(h, kInternal, "output container is null");
+  return Guard(h, [&]() -> int {
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    return JoinLines(h, d_text, d_text_offsets, n, d_out, out_capacity, static_cast<hipStream_t>(stream), out_bytes);
+  });
+}
+
+/* ---- ids file -> corpus file (the caller-side loop of spm_decode, src/spm_decode_main.cc) -------------------------------
+ * The inverse of spmx_encode_file, with the same pipeline of worker threads over chunks that end at a line end:
+ *   "id"     pinned staging copy -> H2D -> id-line parser -> Decode -> line joiner -> one D2H of the image -> fwrite
+ *   "bin"    in_path: flat int32 ids, in_path + ".idx": n + 1 uint64 offsets; cut by offsets, then as above behind the parser
+ *   "piece"  lines of space-separated pieces: PieceToId on the host (a piece outside the vocabulary travels as a literal, as
+ *            in spmx_decode_batch_pieces), then Decode and the joiner
+ * A writer keeps the chunks in order.  Of several failing chunks the lowest one's status is returned. */
+namespace {
+struct MappedFile {
+  const uint8_t *p = nullptr;
+  uint64_t size = 0;
+  // 0 ok, 1 cannot open, 2 other
+  int Open(const std::string &path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return 1;
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); return 2; }
+    size = static_cast<uint64_t>(sb.st_size);
+    if (size) {
+      void *m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m == MAP_FAILED) { close(fd); size = 0; return 2; }
+      p = static_cast<const uint8_t *>(m);
+    }
+    close(fd);
+    return 0;
+  }
+  ~MappedFile() { if (p) munmap(const_cast<uint8_t *>(p), size); }
+};
+}  // namespace
+
+int spmx_decode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *input_format, uint64_t *n_lines,
+                     uint64_t *n_ids) {
+  if (!h) return kInvalidArgument;
+  if (n_lines) *n_lines = 0;
+  if (n_ids) *n_ids = 0;
+  return Guard(h, [&]() -> int {
+    const std::string fmt = input_format ? input_format : "id";
+    const bool bin = fmt == "bin", piece = fmt == "piece";
+    if (!bin && !piece && fmt != "id") return Fail(h, kInvalidArgument, "input_format must be \"id\", \"bin\" or \"piece\"");
+    uint64_t target = 64ull << 20;
+    if (const char *e = getenv("SPMX_FILE_CHUNK")) {
+      const unsigned long long v = strtoull(e, nullptr, 10);
+      target = v < 4096 ? 4096 : v;
+    }
+    const std::string in = in_path ? in_path : "";
+    MappedFile file, idx;
+    if (int r = file.Open(in); r != 0)
+      return r == 1 ? Fail(h, kNotFound, "\"" + in + "\": No such file or directory") : Fail(h, kInternal, "cannot map \"" + in + "\"");
+    // chunk k: "id" / "piece" the bytes [cut[k], cut[k + 1]) of the file; "bin" the lines [cut[k], cut[k + 1])
+    std::vector<uint64_t> cut(1, 0);
+    const uint64_t *all_offs = nullptr;
+    if (bin) {
+      if (int r = idx.Open(in + ".idx"); r != 0)
+        return r == 1 ? Fail(h, kNotFound, "\"" + in + ".idx\": No such file or directory") : Fail(h, kInternal, "cannot map \"" + in + ".idx\"");
+      if (idx.size < 8 || idx.size % 8 != 0) return Fail(h, kDataLoss, "\"" + in + ".idx\" does not hold n + 1 64-bit offsets");
+      all_offs = reinterpret_cast<const uint64_t *>(idx.p);
+      const uint64_t n = idx.size / 8 - 1;
+      bool ok = all_offs[n] <= file.size / 4;
+      for (uint64_t i = 0; i < n; ++i) ok = ok && all_offs[i] <= all_offs[i + 1];
+      if (!ok) return Fail(h, kDataLoss, "\"" + in + ".idx\": offsets out of order or past the ids");
+      while (cut.back() < n) {
+        const uint64_t l0 = cut.back();
+        // as many lines as keep 4 bytes per id + 8 per line under the target (one line at least)
+        uint64_t lo = l0 + 1, hi = n;
+        while (lo < hi) {
+          const uint64_t mid = lo + (hi - lo + 1) / 2;
+          if ((all_offs[mid] - all_offs[l0]) * 4 + (mid - l0) * 8 <= target) lo = mid; else hi = mid - 1;
+        }
+        cut.push_back(lo);
+      }
+    } else {
+      while (cut.back() < file.size) {
+        uint64_t e = cut.back() + target;
+        if (e >= file.size) e = file.size;
+        else {
+          const void *nl = memchr(file.p + e, '\n', file.size - e);
+          e = nl ? static_cast<uint64_t>(static_cast<const uint8_t *>(nl) - file.p) + 1 : file.size;
+        }
+        cut.push_back(e);
+      }
+    }
+    FILE *out = fopen(out_path ? out_path : "", "wb");
+    if (!out) return Fail(h, kPermissionDenied, std::string("cannot write \"") + (out_path ? out_path : "") + "\"");
+    const uint64_t n_chunks = cut.size() - 1;
+    int T = h->host_threads < 4 ? h->host_threads : 4;
+    if (static_cast<uint64_t>(T) > n_chunks) T = static_cast<int>(n_chunks ? n_chunks : 1);
+    bool to_unk = false;
+    { std::lock_guard<std::mutex> l(h->mu); to_unk = h->dx_unk; }
+    std::mutex mu;
+    std::condition_variable cv;
+    uint64_t next_write = 0, line_total = 0, id_total = 0;
+    uint64_t fail_chunk = ~0ull;          // the lowest failing chunk so far, its status and text
+    int fail_rc = kOk;
+    std::string fail_err;
+    auto worker = [&](int w) {
+      uint64_t k = static_cast<uint64_t>(w);
+      auto body = [&]() -> int {
+        HIP_OR_RETURN(h, hipSetDevice(h->device));
+        Lease L(h);
+        if (int r = L.Ready(); r != kOk) return r;
+        Workspace *ws = L.ws.get();
+        hipStream_t st = ws->stream;
+        DevBuf<uint8_t> d_file, d_out;
+        struct Guard2 { DevBuf<uint8_t> &a, &b; ~Guard2() { a.Free(); b.Free(); } } g2{d_file, d_out};
+        struct LitGuard { Workspace *w; ~LitGuard() { w->lit_bytes = nullptr; w->lit_offs = nullptr; w->n_lit = 0; } } lit_guard{ws};
+        std::vector<int32_t> ids;
+        std::vector<uint64_t> io;
+        std::vector<uint32_t> lit_offs;
+        std::string lit_bytes;
+        for (; k < n_chunks; k += static_cast<uint64_t>(T)) {
+          { std::lock_guard<std::mutex> l(mu); if (fail_chunk < k) return kOk; }
+          const int32_t *d_ids = nullptr;      // the kernels address d_ids + offsets[i]
+          uint64_t lines = 0, total_ids = 0;
+          if (bin) {
+            const uint64_t l0 = cut[k], base = all_offs[l0];
+            lines = cut[k + 1] - l0;
+            total_ids = all_offs[cut[k + 1]] - base;
+            HIP_OR_RETURN(h, ws->d_ids.Reserve(total_ids + 16));
+            HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 1));
+            if (total_ids) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_ids.p, file.p + base * 4, total_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, all_offs + l0, (lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            d_ids = ws->d_ids.p - base;
+          } else if (piece) {
+            // std::getline and StrSplit(line, " ") without empty tokens, on the host; PieceToId per token
+            const uint8_t *p = file.p + cut[k], *e = file.p + cut[k + 1];
+            ids.clear(); io.assign(1, 0); lit_offs.assign(1, 0); lit_bytes.clear();
+            while (p < e) {
+              const uint8_t *nl = static_cast<const uint8_t *>(memchr(p, '\n', static_cast<size_t>(e - p)));
+              const uint8_t *le = nl ? nl : e;
+              while (p < le) {
+                if (*p == ' ') { ++p; continue; }
+                const uint8_t *sp = static_cast<const uint8_t *>(memchr(p, ' ', static_cast<size_t>(le - p)));
+                const uint8_t *te = sp ? sp : le;
+                const std::string tok(reinterpret_cast<const char *>(p), static_cast<size_t>(te - p));
+                int id = h->model.unk_id;
+                try { id = h->model.PieceToId(tok); } catch (...) {}
+                if (id == h->model.unk_id && tok != h->model.unk_piece && !to_unk) {
+                  if (tok.size() > 0xFFFFu) return Fail(h, kInvalidArgument, "a piece outside the vocabulary is longer than 65535 bytes");
+                  if (lit_offs.size() >= (1ull << 31) || lit_bytes.size() + tok.size() >= (1ull << 32))
+                    return Fail(h, kInvalidArgument, "too many pieces outside the vocabulary in one batch");
+                  lit_bytes += tok;
+                  lit_offs.push_back(static_cast<uint32_t>(lit_bytes.size()));
+                  id = -static_cast<int>(lit_offs.size() - 1);
+                }
+                ids.push_back(id);
+                p = te;
+              }
+              io.push_back(ids.size());
+              p = nl ? nl + 1 : e;
+            }
+            lines = io.size() - 1;
+            total_ids = ids.size();
+            const uint32_t n_lit = static_cast<uint32_t>(lit_offs.size() - 1);
+            HIP_OR_RETURN(h, ws->d_ids.Reserve(total_ids + 16));
+            HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 1));
+            if (total_ids) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_ids.p, ids.data(), total_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, io.data(), (lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            ws->lit_bytes = nullptr; ws->lit_offs = nullptr; ws->n_lit = 0;
+            if (n_lit) {
+              HIP_OR_RETURN(h, ws->d_lit_offs.Reserve(n_lit + 1));
+              HIP_OR_RETURN(h, ws->d_lit_bytes.Reserve(lit_bytes.size() + 16));
+              HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_lit_offs.p, lit_offs.data(), (n_lit + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+              if (!lit_bytes.empty()) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_lit_bytes.p, lit_bytes.data(), lit_bytes.size(), hipMemcpyHostToDevice, st));
+              ws->lit_bytes = ws->d_lit_bytes.p; ws->lit_offs = ws->d_lit_offs.p; ws->n_lit = n_lit;
+            }
+            HIP_OR_RETURN(h, hipStreamSynchronize(st));        // (the vectors are reused by the next chunk)
+            d_ids = ws->d_ids.p;
+          } else {
+            const uint64_t bytes = cut[k + 1] - cut[k];
+            HIP_OR_RETURN(h, ws->h_text.Reserve(bytes + 32));
+            HIP_OR_RETURN(h, d_file.Reserve(bytes + 32));
+            memcpy(ws->h_text.p, file.p + cut[k], bytes);
+            HIP_OR_RETURN(h, hipMemcpyAsync(d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
+            // a token takes two bytes at least but for the image's last one; the lines are a guess the parser corrects
+            HIP_OR_RETURN(h, ws->d_ids.Reserve(bytes / 2 + 16));
+            uint64_t want_offs = bytes / 8 + 1024;
+            int r = kOk;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+              HIP_OR_RETURN(h, ws->d_offs.Reserve(want_offs));
+              r = ParseIdLines(h, ws, d_file.p, bytes, ws->d_ids.p, ws->d_ids.cap, ws->d_offs.p, ws->d_offs.cap, st, &lines, &total_ids);
+              if (r != kResourceExhausted || lines + 1 <= ws->d_offs.cap) break;
+              want_offs = lines + 1;
+            }
+            if (r != kOk) return r;
+            d_ids = ws->d_ids.p;
+          }
+          // Decode -> joiner -> one D2H of the finished image
+          HIP_OR_RETURN(h, ws->d_id_offs.Reserve(lines + 1));
+          uint64_t cap = total_ids * 6 + 64, text_bytes = 0;
+          int r = kOk;
+          for (int attempt = 0; attempt < 2; ++attempt) {
+            HIP_OR_RETURN(h, ws->d_text.Reserve(cap));
+            r = DecodeDevice(h, ws, d_ids, ws->d_offs.p, lines, ws->d_text.p, ws->d_text.cap, ws->d_id_offs.p, st, &text_bytes);
+            if (r != kResourceExhausted || text_bytes <= ws->d_text.cap) break;
+            cap = text_bytes;
+          }
+          if (r != kOk) return r;
+          uint64_t image = 0;
+          HIP_OR_RETURN(h, d_out.Reserve(text_bytes + lines + 32));
+          r = JoinLines(h, ws->d_text.p, ws->d_id_offs.p, lines, d_out.p, d_out.cap, st, &image, &text_bytes);
+          if (r != kOk) return r;
+          HIP_OR_RETURN(h, ws->h_text.Reserve(image + 32));
+          if (image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, d_out.p, image, hipMemcpyDeviceToHost, st));
+          HIP_OR_RETURN(h, hipStreamSynchronize(st));
+          std::unique_lock<std::mutex> l(mu);
+          cv.wait(l, [&] { return next_write == k || fail_chunk < k; });
+          if (fail_chunk < k) return kOk;
+          const bool ok = image == 0 || fwrite(ws->h_text.p, 1, image, out) == image;
+          line_total += lines;
+          id_total += total_ids;
+          next_write = k + 1;
+          cv.notify_all();
+          if (!ok) return Fail(h, kDataLoss, "short write");
+        }
+        return kOk;
+      };
+      int rc = kOk;
+      try { rc = body(); } catch (const std::bad_alloc &) { rc = kResourceExhausted; t_error = "out of host memory"; } catch (...) { rc = kInternal; t_error = "unknown exception"; }
+      if (rc != kOk) {
+        const std::string err = t_error;
+        std::lock_guard<std::mutex> l(mu);
+        if (k < fail_chunk) { fail_chunk = k; fail_rc = rc; fail_err = err; }
+        cv.notify_all();
+      }
+    };
+    std::vector<std::thread> pool;
+    for (int w = 1; w < T; ++w) pool.emplace_back(worker, w);
+    worker(0);
+    for (auto &t : pool) t.join();
+    fclose(out);
+    if (fail_rc != kOk) return Fail(h, fail_rc, fail_err);
+    if (n_lines) *n_lines = line_total;
+    if (n_ids) *n_ids = id_total;
+    return kOk;
+  });
+}
+
 int spmx_set_profiling(spmx_handle *h, int enabled) {
   if (!h) return kInvalidArgument;
   std::lock_guard<std::mutex> l(h->mu);
@@ -3529,4 +3869,5 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
 #ifdef SPMX_WAVE_API
 // (the test suite's wavefront emulator builds this file against its own launchers: tests/emu)
 #include "../../tests/emu/emu_launch_charword.h"
+#include "../../tests/emu/emu_launch_idtext.h"
 #endif

@@ -1380,5 +1380,6 @@ SPMX_DEVICE void compact_big_block(const CompactArgs &a) {
 #include "kernels_uniwave.h"
 #include "kernels_charwave.h"
 #include "kernels_gather.h"
+#include "kernels_idtext.h"
 
 #endif

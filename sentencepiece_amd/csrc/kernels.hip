@@ -163,6 +163,9 @@ __global__ __launch_bounds__(64) void CompactBigKernel(CompactArgs a) { compact_
 __global__ __launch_bounds__(64) void RebaseOffsetsKernel(RebaseArgs a) { rebase_block(a); }
 __global__ __launch_bounds__(64) void PackIdsKernel(PackArgs a) { pack_block(a); }
 __global__ __launch_bounds__(64) void UnpackIdsKernel(UnpackArgs a) { unpack_block(a); }
+__global__ __launch_bounds__(64) void ParseIdsCountKernel(ParseIdsArgs a) { parse_ids_block<false>(a); }
+__global__ __launch_bounds__(64) void ParseIdsWriteKernel(ParseIdsArgs a) { parse_ids_block<true>(a); }
+__global__ __launch_bounds__(64) void JoinLinesKernel(JoinLinesArgs a) { join_lines_block(a); }
 
 namespace {
 using EncodeFn = void (*)(EncodeArgs);
@@ -356,6 +359,16 @@ hipError_t LaunchPackIds(const PackArgs &a, int grid, hipStream_t stream) {
 }
 hipError_t LaunchUnpackIds(const UnpackArgs &a, int grid, hipStream_t stream) {
   hipLaunchKernelGGL(UnpackIdsKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t LaunchParseIdLines(bool write, const ParseIdsArgs &a, int grid, hipStream_t stream) {
+  if (write) hipLaunchKernelGGL(ParseIdsWriteKernel, dim3(grid), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(ParseIdsCountKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t LaunchJoinLines(const JoinLinesArgs &a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(JoinLinesKernel, dim3(grid), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

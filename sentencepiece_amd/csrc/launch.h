@@ -71,6 +71,9 @@ hipError_t LaunchRebase(const RebaseArgs &a, int grid, hipStream_t stream);   //
 // the packed gather's two streaming kernels (kernels_gather.h pack_block / unpack_block); workgroups of one wavefront
 hipError_t LaunchPackIds(const PackArgs &a, int grid, hipStream_t stream);
 hipError_t LaunchUnpackIds(const UnpackArgs &a, int grid, hipStream_t stream);
+// the file side of Decode (kernels_idtext.h): id lines -> CSR ids (count pass / write pass), packed text -> lines with '\n'
+hipError_t LaunchParseIdLines(bool write, const ParseIdsArgs &a, int grid, hipStream_t stream);
+hipError_t LaunchJoinLines(const JoinLinesArgs &a, int grid, hipStream_t stream);
 
 }  // namespace spmx
 #endif

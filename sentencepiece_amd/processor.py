@@ -1288,6 +1288,65 @@ class SentencePieceProcessor:
         self._check(rc)
         return d_text[:tb.value], d_offs[:n.value + 1], n.value
 
+    # ------------------------------------------------ corpus file side of Decode ----
+    def ParseIdLinesDevice(self, d_file, stream=None):
+        """A file image of id lines on the GPU (torch uint8 tensor; what ``EncodeFile(..., "id")`` and the reference's
+        ``spm_encode --output_format=id`` write) -> ``(d_ids int32, d_id_offsets int64[n + 1], n_lines, n_ids)``, the CSR
+        form ``DecodeDevice`` takes.  Lines are std::getline's, tokens the runs of bytes other than ``' '``, values
+        glibc's ``atoi`` (the loop of the reference's ``spm_decode --input_format=id``)."""
+        import torch
+        self._need()
+        nbytes = d_file.numel()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_file.device).cuda_stream
+        n, t = C.c_uint64(0), C.c_uint64(0)
+        d_ids = torch.empty(nbytes // 2 + 16, dtype=torch.int32, device=d_file.device)
+        d_offs = torch.empty(nbytes // 8 + 1024, dtype=torch.int64, device=d_file.device)
+        for _ in range(2):
+            rc = self._lib.spmx_parse_id_lines_device(self._h, d_file.data_ptr(), nbytes, d_ids.data_ptr(), d_ids.numel(),
+                                                      d_offs.data_ptr(), d_offs.numel(), stream, C.byref(n), C.byref(t))
+            if rc == _RESOURCE_EXHAUSTED:
+                d_offs = torch.empty(n.value + 1, dtype=torch.int64, device=d_file.device)
+                if t.value > d_ids.numel():
+                    d_ids = torch.empty(t.value, dtype=torch.int32, device=d_file.device)
+                continue
+            break
+        self._check(rc)
+        return d_ids[:t.value], d_offs[:n.value + 1], n.value, t.value
+
+    def JoinLinesDevice(self, d_text, d_text_offsets, stream=None):
+        """Packed text on the GPU (``d_text`` uint8, ``d_text_offsets`` int64[n + 1] starting at 0, as ``DecodeDevice``
+        returns them) -> the file image ``d_file`` (uint8): every line followed by ``'\\n'``.  The inverse of
+        ``SplitLinesDevice``."""
+        import torch
+        self._need()
+        n = d_text_offsets.numel() - 1
+        if stream is None:
+            stream = torch.cuda.current_stream(d_text.device).cuda_stream
+        need = C.c_uint64(0)
+        d_out = torch.empty(d_text.numel() + n + 16, dtype=torch.uint8, device=d_text.device)
+        for _ in range(2):
+            rc = self._lib.spmx_join_lines_device(self._h, d_text.data_ptr(), d_text_offsets.data_ptr(), n, d_out.data_ptr(),
+                                                  d_out.numel(), stream, C.byref(need))
+            if rc == _RESOURCE_EXHAUSTED and need.value > d_out.numel():
+                d_out = torch.empty(need.value, dtype=torch.uint8, device=d_text.device)
+                continue
+            break
+        self._check(rc)
+        return d_out[:need.value]
+
+    def DecodeFile(self, in_path, out_path, input_format="id"):
+        """Ids file -> corpus file, the loop of the reference's ``spm_decode`` (spm_decode_main.cc) as one pipelined call
+        and the inverse of ``EncodeFile``: ``input_format="id"`` reads lines of space-separated decimal ids (parsed on
+        the device), ``"bin"`` the flat int32 ids of ``in_path`` with the uint64 offsets of ``in_path + ".idx"``,
+        ``"piece"`` lines of space-separated pieces.  Every decoded line is written with a ``'\\n'``.
+        ``SetDecodeExtraOptions`` applies.  Returns ``(lines, ids)``."""
+        self._need()
+        nl, ni = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.spmx_decode_file(self._h, os.fsencode(in_path), os.fsencode(out_path),
+                                               input_format.encode(), C.byref(nl), C.byref(ni)))
+        return int(nl.value), int(ni.value)
+
     # ------------------------------------------------------ measurement ----
     def _csr_call(self, fn, text, offsets, *mid):
         text = np.ascontiguousarray(text, dtype=np.uint8)
