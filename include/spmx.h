@@ -431,9 +431,12 @@ int spmx_split_lines_device(spmx_handle *h, const void *d_file, uint64_t bytes, 
 /* ---- corpus file -> ids --------------------------------------------------
  * What the reference's `spm_encode --output_format=id < in > out` does (src/spm_encode_main.cc:115-119, :159-165: getline,
  * Encode, StrJoin(ids, " ")), as one call: the file is mmap'ed and goes through a pipeline of worker threads -- pinned
- * staging, H2D, the device line splitter, the encode kernels, D2H, formatting -- chunk by chunk, in order.
- * format "id": the reference's text output, byte for byte; "bin": out_path receives the ids (int32, flat) and
- * out_path + ".idx" the n + 1 uint64 offsets. */
+ * staging, H2D, the device line splitter, the encode kernels, the token-text kernels, one D2H of the finished image --
+ * chunk by chunk (64 MiB, SPMX_FILE_CHUNK as in spmx_decode_file), in order.
+ * format "id": the reference's text output, byte for byte; "piece": what `spm_encode` writes without a format flag
+ * (--output_format=piece, :110-114: the pieces joined with ' '); "bin": out_path receives the ids (int32, flat) and
+ * out_path + ".idx" the n + 1 uint64 offsets.  NULL: "id".  The encode extra options apply to every format.  A sentence
+ * that fails by itself has no ids and becomes an empty line. */
 int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *format, uint64_t *n_sentences,
                      uint64_t *n_ids);
 
@@ -455,6 +458,33 @@ int spmx_parse_id_lines_device(spmx_handle *h, const void *d_file, uint64_t byte
  * (or d_out NULL) -> RESOURCE_EXHAUSTED (8) with the needed size in *out_bytes.  d_out may have any alignment. */
 int spmx_join_lines_device(spmx_handle *h, const void *d_text, const uint64_t *d_text_offsets, uint64_t n, void *d_out,
                            uint64_t out_capacity, void *stream, uint64_t *out_bytes);
+
+/* ---- token text: the output side of spm_encode on the device ---------------
+ * The inverse of the parser: CSR ids -> a file image of id lines, absl::StrJoin(ids, " ") + '\n' per line
+ * (src/spm_encode_main.cc:116-119); a line without ids is a single '\n'.  Every int32 is written (a negative id with '-'),
+ * so spmx_parse_id_lines_device of the image gives the CSR back.  Too small a capacity (or d_out NULL) ->
+ * RESOURCE_EXHAUSTED (8) with the needed size in *out_bytes.  n == 0: an empty image.  d_out may have any alignment. */
+int spmx_format_id_lines_device(spmx_handle *h, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, void *d_out,
+                                uint64_t out_capacity, void *stream, uint64_t *out_bytes);
+/* EncodeAsPieces for a batch: text -> ids (as spmx_encode_batch_device) + the pieces' bytes back to back and their
+ * *total_ids + 1 offsets.  A piece is the token's range of the normalized sentence -- an unknown token shows its
+ * characters -- the name of a byte-fallback or control piece, or trainer_spec.unk_piece for an unknown token under the
+ * encode extra option `unk` / `unk_piece` (src/sentencepiece_processor.cc:566-620, :1050-1058).  d_piece_offsets holds
+ * ids_capacity + 1 entries.  Too small an ids_capacity -> RESOURCE_EXHAUSTED (8) with *total_ids (the piece bytes are
+ * not counted then); too small a piece_bytes_capacity (or a NULL buffer) -> 8 with both totals. */
+int spmx_encode_batch_pieces_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets,
+                                    uint64_t n, int32_t *d_ids, uint64_t ids_capacity, uint64_t *d_id_offsets,
+                                    void *d_piece_bytes, uint64_t piece_bytes_capacity, uint64_t *d_piece_offsets,
+                                    void *stream, uint64_t *total_ids, uint64_t *total_piece_bytes);
+/* ... host-buffer form: the four arrays are malloc'ed here (spmx_free) */
+int spmx_encode_batch_pieces(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, int32_t **ids,
+                             uint64_t **id_offsets, char **piece_bytes, uint64_t **piece_offsets);
+/* text -> piece lines: what spm_encode --output_format=piece writes for these sentences, the pieces of a sentence joined
+ * with ' ' and followed by '\n' (an empty sentence: a single '\n').  Capacity protocol as spmx_format_id_lines_device;
+ * *n_ids is the number of pieces. */
+int spmx_encode_piece_lines_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets,
+                                   uint64_t n, void *d_out, uint64_t out_capacity, void *stream, uint64_t *n_ids,
+                                   uint64_t *out_bytes);
 
 /* ---- ids -> corpus file ---------------------------------------------------
  * What the reference's `spm_decode --input_format=id < in > out` does, as one call and as the inverse of

@@ -464,14 +464,47 @@ class SentencePieceProcessor {
     spmx_free(ids); spmx_free(io); spmx_free(b); spmx_free(e); spmx_free(nb); spmx_free(ne); spmx_free(norm); spmx_free(no);
     return FromHandle(rc);
   }
+  // The piece strings alone are composed on the device (spmx_encode_batch_pieces): one std::string per piece here.  A
+  // sentence that yields no piece at all takes the SentencePieceText form, which reports the sentence's own Status.
   virtual util::Status Encode(std::string_view input, std::vector<std::string> *pieces) const {
     if (!h_) return status();
     if (!pieces) return util::Status(util::StatusCode::kInternal, "output container is null");
     pieces->clear();
-    SentencePieceText spt;
-    const util::Status st = Encode(input, &spt);
+    std::vector<std::vector<std::string>> rows;
+    const util::Status st = EncodeAsPiecesBatch({input}, &rows);
     if (!st.ok()) return st;
-    for (auto &p : spt.pieces) pieces->push_back(std::move(p.piece));
+    if (rows[0].empty() && !input.empty()) {
+      SentencePieceText spt;
+      const util::Status own = Encode(input, &spt);
+      if (!own.ok()) return own;
+      for (auto &p : spt.pieces) pieces->push_back(std::move(p.piece));
+      return util::Status();
+    }
+    pieces->swap(rows[0]);
+    return util::Status();
+  }
+  // EncodeAsPieces of every input, beside EncodeBatch: a failing element yields an empty list, as there.
+  util::Status EncodeAsPiecesBatch(const std::vector<std::string_view> &ins, std::vector<std::vector<std::string>> *outs) const {
+    if (!h_) return status();
+    if (!outs) return util::Status(util::StatusCode::kInternal, "output container is null");
+    outs->clear();
+    std::string text;
+    std::vector<uint64_t> offs(ins.size() + 1, 0);
+    for (size_t i = 0; i < ins.size(); ++i) offs[i + 1] = offs[i] + ins[i].size();
+    text.reserve(offs[ins.size()] + 1);
+    for (const std::string_view &s : ins) text.append(s.data() ? s.data() : "", s.size());
+    int32_t *ids = nullptr;
+    uint64_t *io = nullptr, *po = nullptr;
+    char *pb = nullptr;
+    const int rc = spmx_encode_batch_pieces(h_, text.data(), offs.data(), ins.size(), &ids, &io, &pb, &po);
+    if (rc != 0) return FromHandle(rc);
+    outs->resize(ins.size());
+    for (size_t i = 0; i < ins.size(); ++i) {
+      std::vector<std::string> &row = (*outs)[i];
+      row.reserve(io[i + 1] - io[i]);
+      for (uint64_t k = io[i]; k < io[i + 1]; ++k) row.emplace_back(pb + po[k], pb + po[k + 1]);
+    }
+    spmx_free(ids); spmx_free(io); spmx_free(pb); spmx_free(po);
     return util::Status();
   }
   virtual std::vector<std::string> EncodeAsPieces(std::string_view input) const {   // errors are swallowed, as in the reference

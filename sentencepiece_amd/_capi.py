@@ -121,6 +121,14 @@ SYMBOLS = [
     ("spmx_parse_id_lines_device", C.c_int,
      [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),
     ("spmx_join_lines_device", C.c_int, [_H, C.c_void_p, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.POINTER(_U64)]),
+    ("spmx_format_id_lines_device", C.c_int, [_H, C.c_void_p, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.POINTER(_U64)]),
+    ("spmx_encode_batch_pieces_device", C.c_int,
+     [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.c_void_p, _U64, C.c_void_p, C.c_void_p,
+      C.POINTER(_U64), C.POINTER(_U64)]),
+    ("spmx_encode_batch_pieces", C.c_int,
+     [_H, C.c_void_p, C.c_void_p, _U64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("spmx_encode_piece_lines_device", C.c_int,
+     [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),
     ("spmx_decode_file", C.c_int, [_H, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_U64), C.POINTER(_U64)]),
     ("spmx_set_profiling", C.c_int, [_H, C.c_int]),
     ("spmx_last_profile_name", C.c_int, [_H, C.c_int, C.c_char_p, _U64]),

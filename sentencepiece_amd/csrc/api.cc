@@ -236,6 +236,9 @@ struct Workspace {
   DevBuf<uint32_t> d_lit_offs;
   DevBuf<int32_t> d_dec_ids;             // spans form of the host decode calls: the piece ids in output order, the piece offsets
   DevBuf<uint64_t> d_dec_poffs;
+  DevBuf<uint32_t> d_tt_len;             // token text (kernels_tokentext.h): item lengths, records, starts; the normalized text's offsets
+  DevBuf<uint64_t> d_tt_rec, d_tt_start, d_tt_noffs;
+  DevBuf<uint8_t> d_tt_out;              // ... the finished bytes where the caller brings no buffer (the host forms, the file call)
   const uint8_t *lit_bytes = nullptr;    // set for the duration of one spmx_decode_batch_pieces call
   const uint32_t *lit_offs = nullptr;
   uint32_t n_lit = 0;
@@ -263,6 +266,7 @@ struct Workspace {
     d_arena_tb.Free(); d_tok_begin.Free(); d_span_begin.Free(); d_span_end.Free(); d_nspan_begin.Free(); d_nspan_end.Free();
     d_norm.Free(); d_nbest_scratch.Free(); d_slab.Free(); d_pool.Free(); d_sent_status.Free(); d_flags.Free(); d_res_off.Free();
     d_res_score.Free(); d_dyn_tag.Free(); d_dyn_ent.Free(); d_dyn_list.Free(); d_resume.Free(); d_text.Free(); d_offs.Free(); d_id_offs.Free(); d_ids.Free(); d_dn_text.Free(); d_dn_offs.Free();
+    d_tt_len.Free(); d_tt_rec.Free(); d_tt_start.Free(); d_tt_noffs.Free(); d_tt_out.Free();
     h_text.Free(); h_offs.Free(); h_id_offs.Free();
     if (d_ctrl) (void)hipFree(d_ctrl);
     if (h_ctrl) (void)hipHostFree(h_ctrl);
@@ -282,6 +286,8 @@ namespace spmx_tables {   // (a named namespace: spmx_handle, which the public h
 struct DevTables {
   DevBuf<uint32_t> d_ndarts, d_npair, d_sym_final, d_dec_info, d_dec_off;
   DevBuf<uint8_t> d_dec_bytes;
+  DevBuf<uint32_t> d_nm_info, d_nm_off;     // piece names of the token-text kernels (tables.h nm_*)
+  DevBuf<uint8_t> d_nm_bytes;
   DevBuf<uint8_t> d_nblob, d_plen;
   DevBuf<U4> d_ptrie, d_chartab, d_pairtab, d_wordtab, d_umemo, d_umemo16, d_uhot, d_uall, d_uhot2, d_cfirst;
   DevBuf<uint16_t> d_udisp;
@@ -292,6 +298,7 @@ struct DevTables {
   void FreeTables() {
     d_ndarts.Free(); d_npair.Free(); d_sym_final.Free(); d_nblob.Free(); d_ptrie.Free(); d_chartab.Free();
     d_pairtab.Free(); d_wordtab.Free(); d_utrie.Free(); d_sym_len.Free(); d_byte_ids.Free();
+    d_nm_info.Free(); d_nm_off.Free(); d_nm_bytes.Free();
     d_dec_info.Free(); d_dec_off.Free(); d_dec_bytes.Free(); d_plen.Free(); d_cfirst.Free(); d_umemo.Free(); d_umemo16.Free(); d_uall.Free(); d_udisp.Free(); d_uhot2.Free(); d_uhot.Free(); d_pscore.Free();
   }
 };
@@ -461,6 +468,9 @@ int UploadTables(spmx_handle *eh, DevTables *d, const HostTables &t, SpmxDev *de
   HIP_OR_RETURN(eh, Upload(&d->d_dec_info, t.dec_info));
   HIP_OR_RETURN(eh, Upload(&d->d_dec_off, t.dec_off));
   HIP_OR_RETURN(eh, Upload(&d->d_dec_bytes, t.dec_bytes));
+  HIP_OR_RETURN(eh, Upload(&d->d_nm_info, t.nm_info));
+  HIP_OR_RETURN(eh, Upload(&d->d_nm_off, t.nm_off));
+  HIP_OR_RETURN(eh, Upload(&d->d_nm_bytes, t.nm_bytes));
   *dev = t.scalars;
   dev->ndarts = d->d_ndarts.p;
   dev->nblob = d->d_nblob.p;
@@ -527,6 +537,9 @@ int RefreshDevice(spmx_handle *h, bool types_changed) {
     HIP_OR_RETURN(h, Upload(&h->d_dec_info, t.dec_info));
     HIP_OR_RETURN(h, Upload(&h->d_dec_off, t.dec_off));
     HIP_OR_RETURN(h, Upload(&h->d_dec_bytes, t.dec_bytes));
+    HIP_OR_RETURN(h, Upload(&h->d_nm_info, t.nm_info));
+    HIP_OR_RETURN(h, Upload(&h->d_nm_off, t.nm_off));
+    HIP_OR_RETURN(h, Upload(&h->d_nm_bytes, t.nm_bytes));
   }
   SpmxDev d = t.scalars;
   d.ndarts = h->dev.ndarts; d.nblob = h->dev.nblob; d.npair = h->dev.npair; d.ptrie = h->d_ptrie.p; d.cfirst = t.cfirst.empty() ? nullptr : h->d_cfirst.p; d.plen = h->d_plen.p; d.utrie = h->dev.utrie;
@@ -3322,20 +3335,265 @@ int spmx_split_lines_device(spmx_handle *h, const void *d_file, uint64_t bytes, 
   });
 }
 
+/* ---- an encoded batch -> token text: id lines, piece lines, packed pieces (kernels_tokentext.h) -------------------------- */
+namespace {
+// the `unk` / `unk_piece` encode extra option: an unknown token's piece is trainer_spec.unk_piece (.cc:1050-1058)
+bool EncodeUnkOption(const spmx_handle *h) {
+  for (std::string rest = h->extra_options; !rest.empty();) {
+    const size_t q = rest.find(':');
+    const std::string o = rest.substr(0, q);
+    if (o == "unk" || o == "unk_piece") return true;
+    rest = q == std::string::npos ? std::string() : rest.substr(q + 1);
+  }
+  return false;
+}
+
+// where the pieces' bytes come from: the spans of the encode call and the batch's normalized text
+struct PieceSource {
+  const uint32_t *nbegin, *nend;
+  const uint8_t *norm;
+  const uint64_t *norm_offs;
+};
+
+// length pass -> scan -> (the host reads the size) -> write pass.  fmt 0: decimal ids, 1: pieces (src); T = id_offsets[n].
+// d_start: where the item starts go (packed form: the T + 1 piece offsets), null: the workspace's.  d_out null and `grow`
+// set: the bytes go to *grow, sized here.  *out_bytes is the needed size also where out_capacity does not suffice.
+int TokenText(spmx_handle *h, Workspace *ws, int fmt, bool lines, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n,
+              uint64_t T, const PieceSource *src, uint64_t *d_start, void *d_out, uint64_t out_capacity, DevBuf<uint8_t> *grow,
+              hipStream_t stream, uint64_t *out_bytes) {
+  *out_bytes = 0;
+  const uint64_t items = lines ? T + n : T;
+  if (items >= (1ull << 32) - 64) return Fail(h, kInvalidArgument, "more than 2^32 - 64 tokens and lines in one call");
+  if (items == 0) {
+    if (d_start) {
+      HIP_OR_RETURN(h, hipMemsetAsync(d_start, 0, sizeof(uint64_t), stream));
+      HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+    }
+    return kOk;
+  }
+  HIP_OR_RETURN(h, ws->d_tt_len.Reserve(items));
+  HIP_OR_RETURN(h, ws->d_tt_rec.Reserve(items));
+  if (!d_start) { HIP_OR_RETURN(h, ws->d_tt_start.Reserve(items + 1)); d_start = ws->d_tt_start.p; }
+  HIP_OR_RETURN(h, ws->d_tile_sums.Reserve((items + kScanTile - 1) / kScanTile + 2));
+  TokenTextArgs a{};
+  a.ids = d_ids; a.id_offs = d_id_offsets; a.n = n; a.items = items;
+  if (src) { a.nbegin = src->nbegin; a.nend = src->nend; a.norm = src->norm; a.norm_offs = src->norm_offs; }
+  a.nm_info = h->d_nm_info.p; a.nm_off = h->d_nm_off.p; a.nm_bytes = h->d_nm_bytes.p;
+  a.vocab = static_cast<uint32_t>(h->model.pieces.size());
+  a.unk_name = EncodeUnkOption(h) ? 1u : 0u;
+  a.len = ws->d_tt_len.p; a.rec = ws->d_tt_rec.p; a.start = d_start;
+  const uint64_t wide = static_cast<uint64_t>(h->n_cu) * 16;
+  const uint64_t lchunks = (items + kTtItemChunk - 1) / kTtItemChunk;
+  HIP_OR_RETURN(h, LaunchTokenText(fmt, lines, false, a, static_cast<int>(lchunks < wide ? lchunks : wide), stream));
+  {
+    ScanArgs sa{ws->d_tt_len.p, static_cast<uint32_t>(items), ws->d_tile_sums.p, d_start};
+    const uint32_t tiles = (static_cast<uint32_t>(items) + kScanTile - 1) / kScanTile;
+    HIP_OR_RETURN(h, LaunchScan(sa, static_cast<int>(tiles < static_cast<uint32_t>(h->n_cu * 8) ? tiles : h->n_cu * 8), stream));
+  }
+  uint64_t total = 0;
+  HIP_OR_RETURN(h, hipMemcpyAsync(&total, d_start + items, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  *out_bytes = total;
+  if (total == 0) return kOk;
+  if (!d_out && grow) {
+    HIP_OR_RETURN(h, grow->Reserve(total + 16));
+    d_out = grow->p;
+    out_capacity = grow->cap;
+  }
+  if (!d_out || out_capacity < total) return Fail(h, kResourceExhausted, "out_capacity is too small");
+  a.out = static_cast<uint8_t *>(d_out); a.out_bytes = total;
+  const uint64_t wchunks = (total + 15 + kTtOutChunk - 1) / kTtOutChunk;
+  HIP_OR_RETURN(h, LaunchTokenText(fmt, lines, true, a, static_cast<int>(wchunks < wide ? wchunks : wide), stream));
+  HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  return kOk;
+}
+
+// Encode in the spans form and Normalize: what the piece writer reads.  The normalized spans land in the workspace's
+// d_nspan_*, the normalized text in d_norm (16 bytes of slack behind it) and its offsets in d_tt_noffs.
+int EncodeForPieces(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                    int32_t *d_ids, uint64_t ids_capacity, uint64_t *d_id_offsets, hipStream_t stream, uint64_t *total_ids,
+                    PieceSource *src) {
+  const uint64_t cap = d_ids && ids_capacity ? ids_capacity : 1;
+  HIP_OR_RETURN(h, ws->d_span_begin.Reserve(cap));
+  HIP_OR_RETURN(h, ws->d_span_end.Reserve(cap));
+  HIP_OR_RETURN(h, ws->d_nspan_begin.Reserve(cap));
+  HIP_OR_RETURN(h, ws->d_nspan_end.Reserve(cap));
+  if (int rc = EncodeDevice(h, ws, d_text, text_bytes, d_offsets, n, d_ids, d_ids ? ids_capacity : 0, d_id_offsets, nullptr, stream,
+                            total_ids, nullptr, ws->d_span_begin.p, ws->d_span_end.p, ws->d_nspan_begin.p, ws->d_nspan_end.p);
+      rc != kOk)
+    return rc;
+  HIP_OR_RETURN(h, ws->d_tt_noffs.Reserve(n + 1));
+  uint64_t ncap = 2 * text_bytes + 4 * n + 64, ntotal = 0;
+  int rc = kOk;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    HIP_OR_RETURN(h, ws->d_norm.Reserve(ncap + 16));
+    rc = NormalizeDevice(h, ws, d_text, d_offsets, n, ws->d_norm.p, ws->d_norm.cap - 16, ws->d_tt_noffs.p, nullptr, stream, &ntotal);
+    if (rc != kResourceExhausted || ntotal + 16 <= ws->d_norm.cap) break;
+    ncap = ntotal;
+  }
+  if (rc != kOk) return rc;
+  *src = PieceSource{ws->d_nspan_begin.p, ws->d_nspan_end.p, ws->d_norm.p, ws->d_tt_noffs.p};
+  return kOk;
+}
+
+// text -> piece lines with the ids in the workspace (d_ids, d_id_offs); d_out null: the image goes to ws->d_tt_out
+int PieceLines(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+               void *d_out, uint64_t out_capacity, bool grow, hipStream_t stream, uint64_t *n_ids, uint64_t *out_bytes) {
+  *n_ids = 0;
+  *out_bytes = 0;
+  if (n == 0) return kOk;
+  HIP_OR_RETURN(h, ws->d_id_offs.Reserve(n + 1));
+  uint64_t want = IdsGuess(h, text_bytes, n), total = 0;
+  PieceSource src{};
+  int rc = kOk;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
+    rc = EncodeForPieces(h, ws, d_text, text_bytes, d_offsets, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p, stream, &total, &src);
+    if (rc != kResourceExhausted || total <= ws->d_ids.cap) break;
+    want = total;
+  }
+  if (rc != kOk) return rc;
+  *n_ids = total;
+  return TokenText(h, ws, 1, true, ws->d_ids.p, ws->d_id_offs.p, n, total, &src, nullptr, d_out, out_capacity,
+                   grow ? &ws->d_tt_out : nullptr, stream, out_bytes);
+}
+}  // namespace
+
+int spmx_format_id_lines_device(spmx_handle *h, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, void *d_out,
+                                uint64_t out_capacity, void *stream_v, uint64_t *out_bytes) {
+  if (!h) return kInvalidArgument;
+  if (!out_bytes) return Fail(h, kInternal, "output container is null");
+  *out_bytes = 0;
+  return Guard(h, [&]() -> int {
+    if (n == 0) return kOk;
+    if (!d_id_offsets) return Fail(h, kInvalidArgument, "null offsets");
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    uint64_t T = 0;
+    HIP_OR_RETURN(h, hipMemcpyAsync(&T, d_id_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+    if (T && !d_ids) return Fail(h, kInvalidArgument, "null ids");
+    return TokenText(h, L.ws.get(), 0, true, d_ids, d_id_offsets, n, T, nullptr, nullptr, d_out, out_capacity, nullptr, stream, out_bytes);
+  });
+}
+
+int spmx_encode_batch_pieces_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                                    int32_t *d_ids, uint64_t ids_capacity, uint64_t *d_id_offsets, void *d_piece_bytes,
+                                    uint64_t piece_bytes_capacity, uint64_t *d_piece_offsets, void *stream_v, uint64_t *total_ids,
+                                    uint64_t *total_piece_bytes) {
+  if (!h) return kInvalidArgument;
+  if (!total_ids || !total_piece_bytes) return Fail(h, kInternal, "output container is null");
+  *total_ids = 0;
+  *total_piece_bytes = 0;
+  return Guard(h, [&]() -> int {
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    Workspace *ws = L.ws.get();
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    PieceSource src{};
+    if (int rc = EncodeForPieces(h, ws, static_cast<const uint8_t *>(d_text), text_bytes, d_offsets, n, d_ids, ids_capacity, d_id_offsets,
+                                 stream, total_ids, &src);
+        rc != kOk)
+      return rc;
+    // (the ids fit: *total_ids <= ids_capacity; d_piece_offsets holds ids_capacity + 1 entries)
+    const int rc = TokenText(h, ws, 1, false, d_ids, d_id_offsets, n, *total_ids, &src, d_piece_offsets, d_piece_bytes, piece_bytes_capacity,
+                             nullptr, stream, total_piece_bytes);
+    if (rc == kOk && !d_piece_offsets && *total_ids) return Fail(h, kResourceExhausted, "null piece offsets");
+    return rc;
+  });
+}
+
+int spmx_encode_piece_lines_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                                   void *d_out, uint64_t out_capacity, void *stream_v, uint64_t *n_ids, uint64_t *out_bytes) {
+  if (!h) return kInvalidArgument;
+  if (!n_ids || !out_bytes) return Fail(h, kInternal, "output container is null");
+  *n_ids = 0;
+  *out_bytes = 0;
+  return Guard(h, [&]() -> int {
+    if (n && !d_offsets) return Fail(h, kInvalidArgument, "null offsets");
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    return PieceLines(h, L.ws.get(), static_cast<const uint8_t *>(d_text), text_bytes, d_offsets, n, d_out, out_capacity, false,
+                      static_cast<hipStream_t>(stream_v), n_ids, out_bytes);
+  });
+}
+
+int spmx_encode_batch_pieces(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, int32_t **ids,
+                             uint64_t **id_offsets, char **piece_bytes, uint64_t **piece_offsets) {
+  if (!h) return kInvalidArgument;
+  if (!ids || !id_offsets || !piece_bytes || !piece_offsets) return Fail(h, kInternal, "output container is null");
+  *ids = nullptr; *id_offsets = nullptr; *piece_bytes = nullptr; *piece_offsets = nullptr;
+  if (n && !offsets) return Fail(h, kInvalidArgument, "null offsets");
+  return Guard(h, [&]() -> int {
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    Workspace *ws = L.ws.get();
+    hipStream_t st = ws->stream;
+    uint64_t total = 0, pbytes = 0;
+    if (n) {
+      const uint64_t base = offsets[0], text_bytes = offsets[n] - base;
+      HIP_OR_RETURN(h, ws->d_text.Reserve(text_bytes + 32));
+      HIP_OR_RETURN(h, ws->d_offs.Reserve(n + 1));
+      HIP_OR_RETURN(h, ws->d_id_offs.Reserve(n + 1));
+      if (text_bytes) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_text.p, text + base, text_bytes, hipMemcpyHostToDevice, st));
+      HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      const uint8_t *d_text = ws->d_text.p - base;        // (the kernels address text + offs[i]: EncodeBatchHost)
+      uint64_t want = IdsGuess(h, text_bytes, n);
+      PieceSource src{};
+      int rc = kOk;
+      for (int attempt = 0; attempt < 2; ++attempt) {
+        HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
+        rc = EncodeForPieces(h, ws, d_text, text_bytes, ws->d_offs.p, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p, st, &total, &src);
+        if (rc != kResourceExhausted || total <= ws->d_ids.cap) break;
+        want = total;
+      }
+      if (rc != kOk) return rc;
+      rc = TokenText(h, ws, 1, false, ws->d_ids.p, ws->d_id_offs.p, n, total, &src, nullptr, nullptr, 0, &ws->d_tt_out, st, &pbytes);
+      if (rc != kOk) return rc;
+    }
+    int32_t *hi = static_cast<int32_t *>(malloc((total ? total : 1) * sizeof(int32_t)));
+    uint64_t *ho = static_cast<uint64_t *>(malloc((n + 1) * sizeof(uint64_t)));
+    char *hb = static_cast<char *>(malloc(pbytes ? pbytes : 1));
+    uint64_t *hp = static_cast<uint64_t *>(malloc((total + 1) * sizeof(uint64_t)));
+    auto drop = [&]() { free(hi); free(ho); free(hb); free(hp); };
+    if (!hi || !ho || !hb || !hp) { drop(); return Fail(h, kResourceExhausted, "out of host memory"); }
+    ho[0] = 0;
+    hp[0] = 0;
+    hipError_t e = hipSuccess;
+    if (n) e = hipMemcpyAsync(ho, ws->d_id_offs.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(hi, ws->d_ids.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(hp, ws->d_tt_start.p, (total + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && pbytes) e = hipMemcpyAsync(hb, ws->d_tt_out.p, pbytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { drop(); return FailHip(h, e, "hipMemcpy(pieces)"); }
+    *ids = hi; *id_offsets = ho; *piece_bytes = hb; *piece_offsets = hp;
+    return kOk;
+  });
+}
+
 /* ---- corpus file -> ids (the caller-side loop of spm_encode, src/spm_encode_main.cc:159-165) -------------------------
  * mmap the input, cut it into chunks that end at a line end, and run them through a pipeline of worker threads (each
  * with a workspace and a stream): pinned staging copy -> H2D -> spmx_split_lines (getline semantics, on the device)
- * -> encode -> D2H -> format.  A writer keeps the chunks in order.  format "id": one line of space-separated ids per
- * input line, as `spm_encode --output_format=id` writes; "bin": out_path gets the ids (int32, flat), out_path + ".idx"
- * the n + 1 uint64 offsets. */
+ * -> encode -> format -> D2H.  A writer keeps the chunks in order.  format "id": one line of space-separated ids per
+ * input line, as `spm_encode --output_format=id` writes; "piece": the pieces joined with ' ', spm_encode's default; both
+ * images are written on the device (kernels_tokentext.h) and come back in one D2H.  "bin": out_path gets the ids (int32,
+ * flat), out_path + ".idx" the n + 1 uint64 offsets.  SPMX_FILE_CHUNK sets the chunk size (spmx_decode_file);
+ * SPMX_ID_HOST_FORMAT=1 keeps the ids of format "id" on the host's formatting loop (A/B). */
 int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *format, uint64_t *n_sentences,
                      uint64_t *n_ids) {
   if (!h) return kInvalidArgument;
   if (n_sentences) *n_sentences = 0;
   if (n_ids) *n_ids = 0;
   return Guard(h, [&]() -> int {
-    const bool bin = format && std::string(format) == "bin";
-    if (format && !bin && std::string(format) != "id") return Fail(h, kInvalidArgument, "format must be \"id\" or \"bin\"");
+    const std::string fmt = format ? format : "id";
+    const bool bin = fmt == "bin", piece = fmt == "piece";
+    if (!bin && !piece && fmt != "id") return Fail(h, kInvalidArgument, "format must be \"id\", \"piece\" or \"bin\"");
+    const bool host_format = getenv("SPMX_ID_HOST_FORMAT") != nullptr;
     const int fd = open(in_path ? in_path : "", O_RDONLY);
     if (fd < 0) return Fail(h, kNotFound, std::string("\"") + (in_path ? in_path : "") + "\": No such file or directory");
     struct stat sb;
@@ -3358,7 +3616,11 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
     }
     // chunks of about 64 MiB that end after a line end
     std::vector<uint64_t> cut(1, 0);
-    const uint64_t target = 64ull << 20;
+    uint64_t target = 64ull << 20;
+    if (const char *e = getenv("SPMX_FILE_CHUNK")) {
+      const unsigned long long v = strtoull(e, nullptr, 10);
+      target = v < 4096 ? 4096 : v;
+    }
     while (cut.back() < size) {
       uint64_t e = cut.back() + target;
       if (e >= size) e = size;
@@ -3409,21 +3671,37 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
           uint64_t n_lines = 0, text_bytes = 0;
           int r = spmx_split_lines_device(h, d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &n_lines, &text_bytes);
           if (r != kOk) return r;
-          uint64_t want = IdsGuess(h, text_bytes, n_lines), total = 0;
-          for (int attempt = 0; attempt < 2; ++attempt) {
-            HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
-            r = EncodeDevice(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
-                             nullptr, st, &total, nullptr);
-            if (r != kResourceExhausted || total <= ws->d_ids.cap) break;
-            want = total;
+          uint64_t want = IdsGuess(h, text_bytes, n_lines), total = 0, image = 0;
+          if (piece) {
+            r = PieceLines(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, nullptr, 0, true, st, &total, &image);
+            if (r != kOk) return r;
+          } else {
+            for (int attempt = 0; attempt < 2; ++attempt) {
+              HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
+              r = EncodeDevice(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
+                               nullptr, st, &total, nullptr);
+              if (r != kResourceExhausted || total <= ws->d_ids.cap) break;
+              want = total;
+            }
+            if (r != kOk) return r;
           }
-          if (r != kOk) return r;
-          ids.resize(total);
-          io.resize(n_lines + 1);
-          if (total) HIP_OR_RETURN(h, hipMemcpyAsync(ids.data(), ws->d_ids.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-          HIP_OR_RETURN(h, hipMemcpyAsync(io.data(), ws->d_id_offs.p, (n_lines + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-          HIP_OR_RETURN(h, hipStreamSynchronize(st));
-          if (!bin) {                                  // absl::StrJoin(ids, " ") per line (spm_encode_main.cc:116-119)
+          const bool device_image = piece || (!bin && !host_format);
+          if (device_image) {                          // the finished image in one D2H
+            if (!piece) {
+              r = TokenText(h, ws, 0, true, ws->d_ids.p, ws->d_id_offs.p, n_lines, total, nullptr, nullptr, nullptr, 0, &ws->d_tt_out, st, &image);
+              if (r != kOk) return r;
+            }
+            HIP_OR_RETURN(h, ws->h_text.Reserve(image + 32));
+            if (image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, ws->d_tt_out.p, image, hipMemcpyDeviceToHost, st));
+            HIP_OR_RETURN(h, hipStreamSynchronize(st));
+          } else {
+            ids.resize(total);
+            io.resize(n_lines + 1);
+            if (total) HIP_OR_RETURN(h, hipMemcpyAsync(ids.data(), ws->d_ids.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_OR_RETURN(h, hipMemcpyAsync(io.data(), ws->d_id_offs.p, (n_lines + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            HIP_OR_RETURN(h, hipStreamSynchronize(st));
+          }
+          if (!bin && !device_image) {                            // absl::StrJoin(ids, " ") per line (spm_encode_main.cc:116-119)
             formatted.clear();
             formatted.reserve(total * 6 + n_lines);
             char tmp[16];
@@ -3445,6 +3723,8 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
             if (total) ok = fwrite(ids.data(), sizeof(int32_t), total, out) == total;
             for (uint64_t s2 = 0; s2 < n_lines; ++s2) io[s2] += id_total;
             if (n_lines) ok = ok && fwrite(io.data(), sizeof(uint64_t), n_lines, idx) == n_lines;
+          } else if (device_image) {
+            ok = image == 0 || fwrite(ws->h_text.p, 1, image, out) == image;
           } else if (!formatted.empty()) {
             ok = fwrite(formatted.data(), 1, formatted.size(), out) == formatted.size();
           }
@@ -3582,6 +3862,7 @@ int spmx_join_lines_device(spmx_handle *h, const void *d_text, const uint64_t *d
     return JoinLines(h, d_text, d_text_offsets, n, d_out, out_capacity, static_cast<hipStream_t>(stream), out_bytes);
   });
 }
+
 
 /* ---- ids file -> corpus file (the caller-side loop of spm_decode, src/spm_decode_main.cc) -------------------------------
  * The inverse of spmx_encode_file, with the same pipeline of worker threads over chunks that end at a line end:
@@ -3870,4 +4151,5 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
 // (the test suite's wavefront emulator builds this file against its own launchers: tests/emu)
 #include "../../tests/emu/emu_launch_charword.h"
 #include "../../tests/emu/emu_launch_idtext.h"
+#include "../../tests/emu/emu_launch_tokentext.h"
 #endif

@@ -1381,5 +1381,6 @@ SPMX_DEVICE void compact_big_block(const CompactArgs &a) {
 #include "kernels_charwave.h"
 #include "kernels_gather.h"
 #include "kernels_idtext.h"
+#include "kernels_tokentext.h"
 
 #endif

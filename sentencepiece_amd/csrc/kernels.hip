@@ -166,6 +166,13 @@ __global__ __launch_bounds__(64) void UnpackIdsKernel(UnpackArgs a) { unpack_blo
 __global__ __launch_bounds__(64) void ParseIdsCountKernel(ParseIdsArgs a) { parse_ids_block<false>(a); }
 __global__ __launch_bounds__(64) void ParseIdsWriteKernel(ParseIdsArgs a) { parse_ids_block<true>(a); }
 __global__ __launch_bounds__(64) void JoinLinesKernel(JoinLinesArgs a) { join_lines_block(a); }
+// token text (kernels_tokentext.h): FMT 0 decimal ids / 1 pieces; the lines form or (pieces) the packed form
+__global__ __launch_bounds__(64) void IdLinesLenKernel(TokenTextArgs a) { token_len_block<0, true>(a); }
+__global__ __launch_bounds__(64) void IdLinesWriteKernel(TokenTextArgs a) { token_write_block<0, true>(a); }
+__global__ __launch_bounds__(64) void PieceLinesLenKernel(TokenTextArgs a) { token_len_block<1, true>(a); }
+__global__ __launch_bounds__(64) void PieceLinesWriteKernel(TokenTextArgs a) { token_write_block<1, true>(a); }
+__global__ __launch_bounds__(64) void PiecePackedLenKernel(TokenTextArgs a) { token_len_block<1, false>(a); }
+__global__ __launch_bounds__(64) void PiecePackedWriteKernel(TokenTextArgs a) { token_write_block<1, false>(a); }
 
 namespace {
 using EncodeFn = void (*)(EncodeArgs);
@@ -369,6 +376,15 @@ hipError_t LaunchParseIdLines(bool write, const ParseIdsArgs &a, int grid, hipSt
 }
 hipError_t LaunchJoinLines(const JoinLinesArgs &a, int grid, hipStream_t stream) {
   hipLaunchKernelGGL(JoinLinesKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t LaunchTokenText(int fmt, bool lines, bool write, const TokenTextArgs &a, int grid, hipStream_t stream) {
+  using Fn = void (*)(TokenTextArgs);
+  const Fn fn = fmt == 0 ? (write ? IdLinesWriteKernel : IdLinesLenKernel)
+                : lines  ? (write ? PieceLinesWriteKernel : PieceLinesLenKernel)
+                         : (write ? PiecePackedWriteKernel : PiecePackedLenKernel);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -74,6 +74,9 @@ hipError_t LaunchUnpackIds(const UnpackArgs &a, int grid, hipStream_t stream);
 // the file side of Decode (kernels_idtext.h): id lines -> CSR ids (count pass / write pass), packed text -> lines with '\n'
 hipError_t LaunchParseIdLines(bool write, const ParseIdsArgs &a, int grid, hipStream_t stream);
 hipError_t LaunchJoinLines(const JoinLinesArgs &a, int grid, hipStream_t stream);
+// the file side of Encode (kernels_tokentext.h): fmt 0 decimal ids (lines only) / 1 pieces, the lines or the packed form,
+// the length pass or the write pass
+hipError_t LaunchTokenText(int fmt, bool lines, bool write, const TokenTextArgs &a, int grid, hipStream_t stream);
 
 }  // namespace spmx
 #endif

@@ -97,6 +97,21 @@ Status BuildDecodeTables(const ModelData &m, HostTables *t) {
   }
   t->dec_off[V] = static_cast<uint32_t>(t->dec_bytes.size());
   if (t->dec_bytes.empty()) t->dec_bytes.push_back(0);
+  // What EncodeAsPieces writes for an id (src/sentencepiece_processor.cc:566-620, :1050-1058), by the live type as IsByte /
+  // IsControl / IsUnknown read it: the names of the pieces that do not show their normalized text.
+  t->nm_info.assign(V + 1, 0);
+  t->nm_off.assign(V + 1, 0);
+  t->nm_bytes.clear();
+  for (size_t i = 0; i <= V; ++i) {
+    const int type = i < V ? m.pieces[i].type : kUnknown_;
+    if (i < V && type != kControl && type != kByte && type != kUnknown_) continue;      // kNkText
+    const std::string &name = i < V ? m.pieces[i].piece : m.unk_piece;
+    if (name.size() > 0xFFFF) return Status::Error(kUnimplemented, "piece longer than 65535 bytes");
+    t->nm_off[i] = static_cast<uint32_t>(t->nm_bytes.size());
+    t->nm_info[i] = (type == kUnknown_ ? 2u : 1u) | static_cast<uint32_t>(name.size()) << 8;   // kNkUnknown / kNkName
+    t->nm_bytes.insert(t->nm_bytes.end(), name.begin(), name.end());
+  }
+  t->nm_bytes.insert(t->nm_bytes.end(), 16, 0);
   return Status::OK();
 }
 

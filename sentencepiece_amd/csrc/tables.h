@@ -33,6 +33,9 @@ struct HostTables {
   // decode (kernels_decode.h)
   std::vector<uint32_t> dec_info, dec_off;
   std::vector<uint8_t> dec_bytes;
+  // piece names for the token-text kernels (kernels_tokentext.h): V + 1 entries, the last one trainer_spec.unk_piece
+  std::vector<uint32_t> nm_info, nm_off;   // kind | name length << 8; offset into nm_bytes
+  std::vector<uint8_t> nm_bytes;           // the names of the byte-fallback, control and unknown pieces + 16 bytes of slack
   // scalars (pointers are filled in by whoever owns the memory)
   SpmxDev scalars{};
   int max_piece_len = 0;

@@ -643,11 +643,116 @@ class SentencePieceProcessor:
         out = [spt_proto.ImmutableSentencePieceText(r, rows[i], blobs[i]) for i, r in enumerate(raw)]
         return out[0] if single else out
 
+    def EncodePiecesPacked(self, text, offsets):
+        """Packed host arrays -> ``(ids int32, id_offsets uint64[n + 1], piece_bytes uint8, piece_offsets uint64[T + 1])``:
+        ``EncodeAsPieces`` of a batch with the piece strings composed on the device (csrc/kernels_tokentext.h) -- piece
+        ``k`` is ``piece_bytes[piece_offsets[k]:piece_offsets[k + 1]]``.  ``SetEncodeExtraOptions`` applies."""
+        self._need()
+        self._apply(False, False, False)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        p_ids, p_off, p_pb, p_po = (C.c_void_p() for _ in range(4))
+        tp = text.ctypes.data if len(text) else None
+        self._check(self._lib.spmx_encode_batch_pieces(self._h, tp, offs.ctypes.data, n, C.byref(p_ids), C.byref(p_off),
+                                                       C.byref(p_pb), C.byref(p_po)))
+        try:
+            io = np.ctypeslib.as_array(C.cast(p_off, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+            total = int(io[n])
+            po = np.ctypeslib.as_array(C.cast(p_po, C.POINTER(C.c_uint64)), shape=(total + 1,)).copy()
+            nb = int(po[total])
+            ids = (np.ctypeslib.as_array(C.cast(p_ids, C.POINTER(C.c_int32)), shape=(total,)).copy()
+                   if total else np.zeros(0, dtype=np.int32))
+            pb = (np.ctypeslib.as_array(C.cast(p_pb, C.POINTER(C.c_uint8)), shape=(nb,)).copy()
+                  if nb else np.zeros(0, dtype=np.uint8))
+        finally:
+            for p in (p_ids, p_off, p_pb, p_po):
+                self._lib.spmx_free(p)
+        return ids, io, pb, po
+
+    def EncodePiecesDevice(self, d_text, d_offsets, stream=None):
+        """Device-resident form of ``EncodePiecesPacked`` over torch tensors:
+        ``(d_ids int32, d_id_offsets int64[n + 1], d_piece_bytes uint8, d_piece_offsets int64[T + 1], total)``."""
+        import torch
+        self._need()
+        self._apply(False, False, False)
+        n = d_offsets.numel() - 1
+        dev = d_text.device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        d_id_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        cap = self._ids_guess(d_text.numel(), n)
+        pcap = 2 * d_text.numel() + 4 * n + 64
+        total, pbytes = C.c_uint64(0), C.c_uint64(0)
+        for _ in range(3):
+            d_ids = torch.empty(cap, dtype=torch.int32, device=dev)
+            d_po = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            d_pb = torch.empty(pcap + 16, dtype=torch.uint8, device=dev)
+            rc = self._lib.spmx_encode_batch_pieces_device(
+                self._h, d_text.data_ptr(), d_text.numel(), d_offsets.data_ptr(), n, d_ids.data_ptr(), cap,
+                d_id_offsets.data_ptr(), d_pb.data_ptr(), pcap, d_po.data_ptr(), stream, C.byref(total), C.byref(pbytes))
+            if rc == _RESOURCE_EXHAUSTED and (total.value > cap or pbytes.value > pcap):
+                cap, pcap = max(cap, total.value), max(pcap, pbytes.value)
+                continue
+            break
+        self._check(rc)
+        return d_ids[:total.value], d_id_offsets, d_pb[:pbytes.value], d_po[:total.value + 1], total.value
+
+    def FormatIdLinesDevice(self, d_ids, d_id_offsets, stream=None):
+        """CSR ids on the GPU (``d_ids`` int32, ``d_id_offsets`` int64[n + 1]) -> the file image ``d_file`` (uint8) of
+        ``spm_encode --output_format=id``: the ids of a line joined with ``' '``, every line followed by ``'\\n'``.
+        The inverse of ``ParseIdLinesDevice``."""
+        import torch
+        self._need()
+        n = d_id_offsets.numel() - 1
+        if stream is None:
+            stream = torch.cuda.current_stream(d_id_offsets.device).cuda_stream
+        need = C.c_uint64(0)
+        d_out = torch.empty(d_ids.numel() * 6 + n + 16, dtype=torch.uint8, device=d_id_offsets.device)
+        for _ in range(2):
+            rc = self._lib.spmx_format_id_lines_device(self._h, d_ids.data_ptr(), d_id_offsets.data_ptr(), n, d_out.data_ptr(),
+                                                       d_out.numel(), stream, C.byref(need))
+            if rc == _RESOURCE_EXHAUSTED and need.value > d_out.numel():
+                d_out = torch.empty(need.value, dtype=torch.uint8, device=d_id_offsets.device)
+                continue
+            break
+        self._check(rc)
+        return d_out[:need.value]
+
+    def EncodePieceLinesDevice(self, d_text, d_offsets, stream=None):
+        """Packed text on the GPU (as ``SplitLinesDevice`` returns it) -> ``(d_file uint8, n_pieces)``: the file image
+        of ``spm_encode --output_format=piece``, the pieces of a sentence joined with ``' '`` and followed by ``'\\n'``."""
+        import torch
+        self._need()
+        self._apply(False, False, False)
+        n = d_offsets.numel() - 1
+        if stream is None:
+            stream = torch.cuda.current_stream(d_text.device).cuda_stream
+        ni, need = C.c_uint64(0), C.c_uint64(0)
+        d_out = torch.empty(2 * d_text.numel() + 4 * n + 64, dtype=torch.uint8, device=d_text.device)
+        for _ in range(2):
+            rc = self._lib.spmx_encode_piece_lines_device(self._h, d_text.data_ptr(), d_text.numel(), d_offsets.data_ptr(), n,
+                                                          d_out.data_ptr(), d_out.numel(), stream, C.byref(ni), C.byref(need))
+            if rc == _RESOURCE_EXHAUSTED and need.value > d_out.numel():
+                d_out = torch.empty(need.value, dtype=torch.uint8, device=d_text.device)
+                continue
+            break
+        self._check(rc)
+        return d_out[:need.value], ni.value
+
     def EncodeAsPieces(self, input):
-        """``EncodeAsPieces`` (sentencepiece_processor.h:453-456) / ``encode(out_type=str)``: the piece strings."""
+        """``EncodeAsPieces`` (sentencepiece_processor.h:453-456) / ``encode(out_type=str)``: the piece strings, one
+        slice of ``EncodePiecesPacked``'s bytes per piece."""
         single = isinstance(input, (str, bytes))
-        rows = self.EncodeAsSentencePieceText([input] if single else input)
-        out = [[p.decode("utf-8", "surrogateescape") for p, *_ in row] for row in rows]
+        items = [input] if single else list(input)
+        raw = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in items]
+        offs = np.zeros(len(raw) + 1, dtype=np.uint64)
+        if raw:
+            np.cumsum([len(x) for x in raw], out=offs[1:])
+        _, io, pb, po = self.EncodePiecesPacked(np.frombuffer(b"".join(raw), dtype=np.uint8), offs)
+        blob, po, io = pb.tobytes(), po.tolist(), io.tolist()
+        out = [[blob[po[k]:po[k + 1]].decode("utf-8", "surrogateescape") for k in range(io[i], io[i + 1])]
+               for i in range(len(raw))]
         return out[0] if single else out
 
     encode_as_pieces = EncodeAsPieces
@@ -1392,9 +1497,10 @@ class SentencePieceProcessor:
         return self._csr_call(self._lib.spmx_encode_batch_original, text, offsets)
 
     def EncodeFile(self, in_path, out_path, output_format="id"):
-        """Corpus file -> ids, the loop of the reference's ``spm_encode --output_format=id`` (spm_encode_main.cc:115-165)
-        as one pipelined call: ``output_format="id"`` writes the reference's text (one line of space-separated ids per
-        input line), ``"bin"`` the flat int32 ids to ``out_path`` and the uint64 offsets to ``out_path + ".idx"``.
+        """Corpus file -> ids or pieces, the loop of the reference's ``spm_encode`` (spm_encode_main.cc:110-165) as one
+        pipelined call: ``output_format="id"`` writes the text of ``--output_format=id`` (one line of space-separated ids
+        per input line), ``"piece"`` that of ``--output_format=piece``, the reference's default (the pieces joined with
+        ``' '``), ``"bin"`` the flat int32 ids to ``out_path`` and the uint64 offsets to ``out_path + ".idx"``.
         ``SetEncodeExtraOptions`` applies.  Returns ``(sentences, ids)``."""
         self._need()
         self._apply(False, False, False)

@@ -1,7 +1,8 @@
-// spmx_encode: the command line of the reference's spm_encode (src/spm_encode_main.cc) for the one output this engine
-// produces -- ids -- over the C ABI of include/spmx.h: file (or stdin) in, one line of space-separated ids per input
-// line out (--output_format=id, the reference's bytes), or flat binary ids (--output_format=bin).
-//   spmx_encode --model=M [--input=F] [--output=F] [--output_format=id|bin] [--extra_options=bos:eos] [--device=N]
+// spmx_encode: the command line of the reference's spm_encode (src/spm_encode_main.cc) over the C ABI of include/spmx.h:
+// file (or stdin) in; out one line of space-separated ids per input line (--output_format=id, the reference's bytes), one
+// line of space-separated pieces (--output_format=piece, the reference's bytes for its default format), or flat binary
+// ids (--output_format=bin).  The default here is id; the reference's is piece.
+//   spmx_encode --model=M [--input=F] [--output=F] [--output_format=id|piece|bin] [--extra_options=bos:eos] [--device=N]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,7 +29,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "unknown argument: %s\n", a.c_str());
     return 2;
   }
-  if (model.empty()) { fprintf(stderr, "usage: spmx_encode --model=M [--input=F] [--output=F] [--output_format=id|bin] [--extra_options=..]\n"); return 2; }
+  if (model.empty()) { fprintf(stderr, "usage: spmx_encode --model=M [--input=F] [--output=F] [--output_format=id|piece|bin] [--extra_options=..]\n"); return 2; }
   spmx_handle *h = nullptr;
   if (spmx_create_from_file(model.c_str(), device, &h) != 0) { fprintf(stderr, "%s\n", spmx_last_error(nullptr)); return 1; }
   if (!extra.empty() && spmx_set_encode_extra_options(h, extra.c_str()) != 0) { fprintf(stderr, "%s\n", spmx_last_error(h)); return 1; }
