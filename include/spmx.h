@@ -501,6 +501,34 @@ int spmx_encode_piece_lines_device(spmx_handle *h, const void *d_text, uint64_t 
 int spmx_decode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *input_format, uint64_t *n_lines,
                      uint64_t *n_ids);
 
+/* ---- piece frequency counts: spm_encode --generate_vocabulary --------------
+ * The vocabulary workflow of the reference's spm_encode (src/spm_encode_main.cc:80-83, :102-109, :167-172): count how often
+ * every piece is emitted over a corpus, write the counts as a vocabulary file, encode with the rare pieces switched off.
+ * The reference counts piece strings in a map; piece strings are unique in a loaded model, so the counts are a histogram
+ * over ids, filtered by piece type when the file is written.  The reference counts in `int`, the counts here are 64-bit:
+ * the two agree while every count is below 2^31.
+ *
+ * The histogram kernel: d_ids[n_ids] (int32, device, any 4-byte alignment) -> d_counts[GetPieceSize() + 1] (uint64, device),
+ * ADDED to what is there.  d_counts[id] for 0 <= id < GetPieceSize(); the last entry counts every other value.  The call
+ * only enqueues on `stream`: no status word, no host synchronisation.  counts_capacity < GetPieceSize() + 1 (or d_counts
+ * NULL) -> RESOURCE_EXHAUSTED (8), nothing is written.  n_ids == 0: nothing is enqueued. */
+int spmx_count_ids_device(spmx_handle *h, const int32_t *d_ids, uint64_t n_ids, uint64_t *d_counts, uint64_t counts_capacity,
+                          void *stream);
+/* The histogram of a corpus file: the pipeline of spmx_encode_file (mmap, chunks at line ends, SPMX_FILE_CHUNK, up to 4
+ * workers) with the histogram kernel in place of formatting.  Nothing comes back per chunk; the GetPieceSize() + 1 words
+ * come back once and are ADDED to counts (host), so several files accumulate.  The encode extra options and a vocabulary
+ * restriction apply; bos / eos, unknown and control ids are counted here (the raw histogram) and left out by
+ * spmx_write_vocabulary.  Errors as spmx_encode_file. */
+int spmx_count_file(spmx_handle *h, const char *in_path, uint64_t *counts, uint64_t *n_sentences, uint64_t *n_ids);
+/* counts (host, GetPieceSize() + 1) -> the file `spm_encode --generate_vocabulary` writes: one line piece TAB count per
+ * piece that occurred and is neither UNKNOWN nor CONTROL (BYTE and USER_DEFINED pieces are written), by descending count,
+ * equal counts by ascending piece in unsigned byte order (Sorted, src/trainer_interface.h:36-50).  *n_lines: lines written. */
+int spmx_write_vocabulary(spmx_handle *h, const uint64_t *counts, const char *out_path, uint64_t *n_lines);
+/* LoadVocabulary (src/sentencepiece_processor.cc:341-362): lines "token TAB freq"; the tokens whose freq reaches `threshold`
+ * (1 where the line has no second column) become the valid vocabulary (spmx_set_vocabulary: a character or word model
+ * refuses).  A missing file: NOT_FOUND (5); an empty token or a frequency that does not parse: INTERNAL (13). */
+int spmx_load_vocabulary(spmx_handle *h, const char *path, int threshold);
+
 /* ---- measurement --------------------------------------------------------
  * Per-kernel timing of the encode kernels of the LAST profiled encode call on the handle, measured with hipEvents
  * on the call's stream (enable first).  Arrays hold 7 entries ("kernel slots": 0 the streaming launch over the

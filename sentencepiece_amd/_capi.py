@@ -130,6 +130,10 @@ SYMBOLS = [
     ("spmx_encode_piece_lines_device", C.c_int,
      [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),
     ("spmx_decode_file", C.c_int, [_H, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_U64), C.POINTER(_U64)]),
+    ("spmx_count_ids_device", C.c_int, [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p]),
+    ("spmx_count_file", C.c_int, [_H, C.c_char_p, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),
+    ("spmx_write_vocabulary", C.c_int, [_H, C.c_void_p, C.c_char_p, C.POINTER(_U64)]),
+    ("spmx_load_vocabulary", C.c_int, [_H, C.c_char_p, C.c_int]),
     ("spmx_set_profiling", C.c_int, [_H, C.c_int]),
     ("spmx_last_profile_name", C.c_int, [_H, C.c_int, C.c_char_p, _U64]),
     ("spmx_last_phase_cycles", C.c_int, [_H, C.c_void_p]),

@@ -3760,6 +3760,246 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
   });
 }
 
+/* ---- piece frequency counts: spm_encode --generate_vocabulary (kernels_piececount.h) ------------------------------------ */
+namespace {
+// B of the count kernel: SPMX_COUNT_LDS_BINS (test seam, read at every call; floor 64, ceiling the default), at most V
+uint32_t CountBins(const spmx_handle *h) {
+  uint64_t b = kCountLdsBins;
+  if (const char *e = getenv("SPMX_COUNT_LDS_BINS")) {
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    b = v < kCountLdsBinsMin ? kCountLdsBinsMin : (v > kCountLdsBins ? kCountLdsBins : v);
+  }
+  const uint64_t V = h->model.pieces.size();
+  return static_cast<uint32_t>(b < V ? b : V);
+}
+
+// Enqueues the histogram of d_ids[0, n) into d_counts[V + 1] on `stream`.  The grid follows n: a workgroup zeroes and
+// flushes B bins -- about what sweeping 2 B ids costs (4 B of LDS traffic, up to 8 B of atomics against 4 bytes read per
+// id) -- so it is given at least 2 B ids (and at least 8192, two tiles per wavefront at four wavefronts), and at most one
+// workgroup runs per CU; a workgroup has one wavefront per tile of its share, up to kCountMaxWaves.
+int CountIds(spmx_handle *h, const int32_t *d_ids, uint64_t n, unsigned long long *d_counts, hipStream_t stream) {
+  const uint32_t bins = CountBins(h);
+  const uint64_t share = std::max<uint64_t>(8192, 2ull * bins);
+  for (uint64_t done = 0; done < n;) {
+    const uint64_t part = std::min<uint64_t>(n - done, kCountMaxLaunch);
+    CountArgs a{d_ids + done, part, d_counts, static_cast<uint32_t>(h->model.pieces.size()), bins};
+    const uint64_t grid = std::min<uint64_t>((part + share - 1) / share, static_cast<uint64_t>(h->n_cu > 0 ? h->n_cu : 1));
+    const uint64_t per = (part + grid - 1) / grid;
+    const uint64_t waves = std::min<uint64_t>((per + kCountTile - 1) / kCountTile, kCountMaxWaves);
+    HIP_OR_RETURN(h, LaunchCountIds(a, static_cast<int>(grid), static_cast<int>(waves), stream));
+    done += part;
+  }
+  return kOk;
+}
+}  // namespace
+
+int spmx_count_ids_device(spmx_handle *h, const int32_t *d_ids, uint64_t n_ids, uint64_t *d_counts, uint64_t counts_capacity,
+                          void *stream_v) {
+  if (!h) return kInvalidArgument;
+  return Guard(h, [&]() -> int {
+    if (!d_counts || counts_capacity < h->model.pieces.size() + 1) return Fail(h, kResourceExhausted, "counts_capacity is too small");
+    if (n_ids == 0) return kOk;
+    if (!d_ids) return Fail(h, kInvalidArgument, "null ids");
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    return CountIds(h, d_ids, n_ids, reinterpret_cast<unsigned long long *>(d_counts), static_cast<hipStream_t>(stream_v));
+  });
+}
+
+/* The pipeline of spmx_encode_file with the count kernel in place of formatting: nothing comes back per chunk, the workers
+ * share one device histogram (the kernel's adds to it are atomic) and the V + 1 words come back once, after the last chunk. */
+int spmx_count_file(spmx_handle *h, const char *in_path, uint64_t *counts, uint64_t *n_sentences, uint64_t *n_ids) {
+  if (!h) return kInvalidArgument;
+  if (n_sentences) *n_sentences = 0;
+  if (n_ids) *n_ids = 0;
+  return Guard(h, [&]() -> int {
+    if (!counts) return Fail(h, kInternal, "output container is null");
+    const int fd = open(in_path ? in_path : "", O_RDONLY);
+    if (fd < 0) return Fail(h, kNotFound, std::string("\"") + (in_path ? in_path : "") + "\": No such file or directory");
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); return Fail(h, kInternal, "fstat failed"); }
+    const uint64_t size = static_cast<uint64_t>(sb.st_size);
+    const uint8_t *file = nullptr;
+    if (size) {
+      void *m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m == MAP_FAILED) { close(fd); return Fail(h, kInternal, "mmap failed"); }
+      file = static_cast<const uint8_t *>(m);
+    }
+    close(fd);
+    struct Unmap { const uint8_t *p; uint64_t n; ~Unmap() { if (p) munmap(const_cast<uint8_t *>(p), n); } } unmap{file, size};
+    if (size == 0) return kOk;
+    // chunks of about 64 MiB that end after a line end
+    std::vector<uint64_t> cut(1, 0);
+    uint64_t target = 64ull << 20;
+    if (const char *e = getenv("SPMX_FILE_CHUNK")) {
+      const unsigned long long v = strtoull(e, nullptr, 10);
+      target = v < 4096 ? 4096 : v;
+    }
+    while (cut.back() < size) {
+      uint64_t e = cut.back() + target;
+      if (e >= size) e = size;
+      else {
+        const void *nl = memchr(file + e, '\n', size - e);
+        e = nl ? static_cast<uint64_t>(static_cast<const uint8_t *>(nl) - file) + 1 : size;
+      }
+      cut.push_back(e);
+    }
+    const uint64_t n_chunks = cut.size() - 1;
+    int T = h->host_threads < 4 ? h->host_threads : 4;
+    if (static_cast<uint64_t>(T) > n_chunks) T = static_cast<int>(n_chunks ? n_chunks : 1);
+    const uint64_t V = h->model.pieces.size();
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    DevBuf<unsigned long long> d_hist;
+    struct Guard2 { DevBuf<unsigned long long> &b; ~Guard2() { b.Free(); } } gh{d_hist};
+    HIP_OR_RETURN(h, d_hist.Reserve(V + 1));
+    HIP_OR_RETURN(h, hipMemset(d_hist.p, 0, (V + 1) * sizeof(unsigned long long)));
+    HIP_OR_RETURN(h, hipDeviceSynchronize());         // (the workers' streams do not wait for the null stream)
+    std::mutex mu;
+    uint64_t sent_total = 0, id_total = 0;
+    int first_rc = kOk;
+    std::string first_err;
+    auto worker = [&](int w) {
+      auto body = [&]() -> int {
+        HIP_OR_RETURN(h, hipSetDevice(h->device));
+        Lease L(h);
+        if (int r = L.Ready(); r != kOk) return r;
+        Workspace *ws = L.ws.get();
+        hipStream_t st = ws->stream;
+        DevBuf<uint8_t> d_file;
+        struct Guard3 { DevBuf<uint8_t> &b; ~Guard3() { b.Free(); } } g3{d_file};
+        for (uint64_t k = static_cast<uint64_t>(w); k < n_chunks; k += static_cast<uint64_t>(T)) {
+          { std::lock_guard<std::mutex> l(mu); if (first_rc != kOk) return kOk; }
+          const uint64_t bytes = cut[k + 1] - cut[k];
+          const uint8_t *src = file + cut[k];
+          uint64_t nl = 0;
+          for (const uint8_t *p = src, *e = src + bytes; p < e;) {
+            const void *q = memchr(p, '\n', static_cast<size_t>(e - p));
+            if (!q) break;
+            ++nl;
+            p = static_cast<const uint8_t *>(q) + 1;
+          }
+          const uint64_t lines = nl + (bytes && src[bytes - 1] != '\n' ? 1 : 0);
+          HIP_OR_RETURN(h, ws->h_text.Reserve(bytes + 32));
+          HIP_OR_RETURN(h, d_file.Reserve(bytes + 32));
+          HIP_OR_RETURN(h, ws->d_text.Reserve(bytes + 32));
+          HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 2));
+          HIP_OR_RETURN(h, ws->d_id_offs.Reserve(lines + 2));
+          memcpy(ws->h_text.p, src, bytes);
+          HIP_OR_RETURN(h, hipMemcpyAsync(d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
+          uint64_t n_lines = 0, text_bytes = 0;
+          int r = spmx_split_lines_device(h, d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &n_lines, &text_bytes);
+          if (r != kOk) return r;
+          uint64_t want = IdsGuess(h, text_bytes, n_lines), total = 0;
+          for (int attempt = 0; attempt < 2; ++attempt) {
+            HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
+            r = EncodeDevice(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
+                             nullptr, st, &total, nullptr);
+            if (r != kResourceExhausted || total <= ws->d_ids.cap) break;
+            want = total;
+          }
+          if (r != kOk) return r;
+          if (total) {
+            r = CountIds(h, ws->d_ids.p, total, d_hist.p, st);
+            if (r != kOk) return r;
+          }
+          HIP_OR_RETURN(h, hipStreamSynchronize(st));     // (the staging buffer and the id arena are the next chunk's)
+          std::lock_guard<std::mutex> l(mu);
+          sent_total += n_lines;
+          id_total += total;
+        }
+        return kOk;
+      };
+      int rc = kOk;
+      try { rc = body(); } catch (const std::bad_alloc &) { rc = kResourceExhausted; t_error = "out of host memory"; } catch (...) { rc = kInternal; t_error = "unknown exception"; }
+      if (rc != kOk) {
+        const std::string err = t_error;
+        std::lock_guard<std::mutex> l(mu);
+        if (first_rc == kOk) { first_rc = rc; first_err = err; }
+      }
+    };
+    std::vector<std::thread> pool;
+    for (int w = 1; w < T; ++w) pool.emplace_back(worker, w);
+    worker(0);
+    for (auto &t : pool) t.join();
+    if (first_rc != kOk) return Fail(h, first_rc, first_err);
+    std::vector<unsigned long long> got(V + 1);
+    HIP_OR_RETURN(h, hipMemcpy(got.data(), d_hist.p, (V + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i <= V; ++i) counts[i] += got[i];
+    if (n_sentences) *n_sentences = sent_total;
+    if (n_ids) *n_ids = id_total;
+    return kOk;
+  });
+}
+
+/* Sorted(vocab) of the reference (src/trainer_interface.h:36-50) over the ids whose piece the reference counts: neither
+ * IsUnknown nor IsControl (src/spm_encode_main.cc:106), at least one occurrence. */
+int spmx_write_vocabulary(spmx_handle *h, const uint64_t *counts, const char *out_path, uint64_t *n_lines) {
+  if (!h) return kInvalidArgument;
+  if (n_lines) *n_lines = 0;
+  return Guard(h, [&]() -> int {
+    if (!counts) return Fail(h, kInvalidArgument, "null counts");
+    std::vector<std::pair<uint64_t, const std::string *>> rows;
+    for (size_t i = 0; i < h->model.pieces.size(); ++i) {
+      const PieceRec &p = h->model.pieces[i];
+      if (counts[i] && p.type != kUnknown_ && p.type != kControl) rows.emplace_back(counts[i], &p.piece);
+    }
+    // count descending, then the piece ascending as std::string compares: by unsigned bytes
+    std::sort(rows.begin(), rows.end(), [](const auto &a, const auto &b) {
+      return a.first > b.first || (a.first == b.first && *a.second < *b.second);
+    });
+    FILE *out = fopen(out_path ? out_path : "", "wb");
+    if (!out) return Fail(h, kPermissionDenied, std::string("cannot write \"") + (out_path ? out_path : "") + "\"");
+    bool ok = true;
+    for (const auto &r : rows) {
+      ok = ok && fwrite(r.second->data(), 1, r.second->size(), out) == r.second->size();
+      ok = ok && fprintf(out, "\t%llu\n", static_cast<unsigned long long>(r.first)) > 0;
+    }
+    ok = (fclose(out) == 0) && ok;
+    if (!ok) return Fail(h, kDataLoss, "short write");
+    if (n_lines) *n_lines = rows.size();
+    return kOk;
+  });
+}
+
+/* LoadVocabulary (src/sentencepiece_processor.cc:341-362) as include/spmx_processor.h restates it. */
+int spmx_load_vocabulary(spmx_handle *h, const char *path, int threshold) {
+  if (!h) return kInvalidArgument;
+  std::vector<std::string> vocab;
+  const int rc = Guard(h, [&]() -> int {
+    const std::string fn = path ? path : "";
+    FILE *f = fopen(fn.c_str(), "rb");
+    if (!f) return Fail(h, kNotFound, "\"" + fn + "\": No such file or directory");
+    std::string data;
+    char buf[65536];
+    for (size_t r; (r = fread(buf, 1, sizeof(buf), f)) > 0;) data.append(buf, r);
+    fclose(f);
+    for (size_t p = 0; p < data.size();) {
+      size_t q = data.find('\n', p);
+      if (q == std::string::npos) q = data.size();
+      std::string line = data.substr(p, q - p);
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      p = q + 1;
+      const size_t tab = line.find('\t');
+      const std::string tok = line.substr(0, tab);
+      if (tok.empty()) return Fail(h, kInternal, "LoadVocabulary: an empty token");   // CHECK_OR_RETURN(!v[0].empty())
+      long freq = 1;
+      if (tab != std::string::npos) {
+        const size_t tab2 = line.find('\t', tab + 1);
+        const std::string num = line.substr(tab + 1, tab2 == std::string::npos ? std::string::npos : tab2 - tab - 1);
+        char *end = nullptr;
+        freq = strtol(num.c_str(), &end, 10);
+        if (num.empty() || !end || *end != 0) return Fail(h, kInternal, "Could not parse the frequency");
+      }
+      if (freq >= threshold) vocab.push_back(tok);
+    }
+    return kOk;
+  });
+  if (rc != kOk) return rc;
+  std::vector<const char *> p;
+  std::vector<uint64_t> l;
+  for (const auto &v : vocab) { p.push_back(v.data()); l.push_back(v.size()); }
+  return spmx_set_vocabulary(h, p.data(), l.data(), p.size());
+}
+
 /* ---- id lines -> CSR ids, packed text -> lines (kernels_idtext.h) ------------------------------------------------------ */
 namespace {
 // count pass -> two scans -> (host reads the totals and the last byte) -> write pass.  The needed sizes come back in
@@ -4152,4 +4392,5 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
 #include "../../tests/emu/emu_launch_charword.h"
 #include "../../tests/emu/emu_launch_idtext.h"
 #include "../../tests/emu/emu_launch_tokentext.h"
+#include "../../tests/emu/emu_launch_piececount.h"
 #endif

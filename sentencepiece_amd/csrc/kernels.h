@@ -1382,5 +1382,6 @@ SPMX_DEVICE void compact_big_block(const CompactArgs &a) {
 #include "kernels_gather.h"
 #include "kernels_idtext.h"
 #include "kernels_tokentext.h"
+#include "kernels_piececount.h"
 
 #endif

@@ -173,6 +173,11 @@ __global__ __launch_bounds__(64) void PieceLinesLenKernel(TokenTextArgs a) { tok
 __global__ __launch_bounds__(64) void PieceLinesWriteKernel(TokenTextArgs a) { token_write_block<1, true>(a); }
 __global__ __launch_bounds__(64) void PiecePackedLenKernel(TokenTextArgs a) { token_len_block<1, false>(a); }
 __global__ __launch_bounds__(64) void PiecePackedWriteKernel(TokenTextArgs a) { token_write_block<1, false>(a); }
+// the id histogram (kernels_piececount.h): up to 128 KiB of bins, one workgroup per CU
+__global__ __launch_bounds__(64 * kCountMaxWaves) void CountIdsKernel(CountArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  count_ids_block(a, smem);
+}
 
 namespace {
 using EncodeFn = void (*)(EncodeArgs);
@@ -385,6 +390,17 @@ hipError_t LaunchTokenText(int fmt, bool lines, bool write, const TokenTextArgs 
                 : lines  ? (write ? PieceLinesWriteKernel : PieceLinesLenKernel)
                          : (write ? PiecePackedWriteKernel : PiecePackedLenKernel);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t LaunchCountIds(const CountArgs &a, int grid, int waves, hipStream_t stream) {
+  const uint32_t lds_bytes = a.bins * 4u;
+  if (lds_bytes > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(CountIdsKernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(lds_bytes));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(CountIdsKernel, dim3(grid), dim3(64 * waves), lds_bytes, stream, a);
   return hipGetLastError();
 }
 

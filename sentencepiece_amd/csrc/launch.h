@@ -77,6 +77,8 @@ hipError_t LaunchJoinLines(const JoinLinesArgs &a, int grid, hipStream_t stream)
 // the file side of Encode (kernels_tokentext.h): fmt 0 decimal ids (lines only) / 1 pieces, the lines or the packed form,
 // the length pass or the write pass
 hipError_t LaunchTokenText(int fmt, bool lines, bool write, const TokenTextArgs &a, int grid, hipStream_t stream);
+// the id histogram (kernels_piececount.h): workgroups of `waves` <= kCountMaxWaves wavefronts, a.bins * 4 bytes of LDS each
+hipError_t LaunchCountIds(const CountArgs &a, int grid, int waves, hipStream_t stream);
 
 }  // namespace spmx
 #endif

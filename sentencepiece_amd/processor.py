@@ -1509,6 +1509,75 @@ class SentencePieceProcessor:
                                                output_format.encode(), C.byref(ns), C.byref(ni)))
         return int(ns.value), int(ni.value)
 
+    # ------------------------------------------- piece frequency counts ----
+    def LoadVocabulary(self, filename, threshold):
+        """``LoadVocabulary`` (src/sentencepiece_processor.cc:341-362): lines ``token TAB freq``; the tokens whose
+        frequency reaches ``threshold`` (1 where a line has no second column) become the valid vocabulary, as
+        ``SetVocabulary`` of them.  What ``spm_encode --vocabulary=F --vocabulary_threshold=N`` does before it encodes."""
+        self._need()
+        self._check(self._lib.spmx_load_vocabulary(self._h, os.fsencode(filename), int(threshold)))
+        return True
+
+    def CountIdsDevice(self, d_ids, d_counts=None, stream=None):
+        """The histogram of ``d_ids`` (torch int32, any 4-byte alignment) on the GPU: returns ``d_counts`` (int64
+        ``[GetPieceSize() + 1]``, allocated and zeroed when not given, else ADDED to) with ``d_counts[id]`` the occurrences
+        of ``id`` and the last entry those of every value outside ``[0, GetPieceSize())``.  Only enqueues on ``stream``."""
+        import torch
+        self._need()
+        if d_ids.dtype != torch.int32 or not d_ids.is_contiguous():
+            raise ValueError("d_ids must be a contiguous int32 tensor")
+        if d_counts is None:
+            d_counts = torch.zeros(self.GetPieceSize() + 1, dtype=torch.int64, device=d_ids.device)
+        elif d_counts.dtype != torch.int64 or not d_counts.is_contiguous():
+            raise ValueError("d_counts must be a contiguous int64 tensor")
+        if stream is None:
+            stream = torch.cuda.current_stream(d_ids.device).cuda_stream if d_ids.is_cuda else 0
+        self._check(self._lib.spmx_count_ids_device(self._h, d_ids.data_ptr() if d_ids.numel() else None, d_ids.numel(),
+                                                    d_counts.data_ptr(), d_counts.numel(), stream))
+        return d_counts
+
+    def PieceCounts(self, input):
+        """list[str | bytes] -> numpy int64 ``[GetPieceSize() + 1]``: how often every id is emitted when ``input`` is
+        encoded -- the raw histogram, unknown and control ids (bos / eos of the extra options) included.  The batch is
+        encoded on the device and counted there; only the counts come back."""
+        import torch
+        self._need()
+        self._apply(False, False, False)
+        bs = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in input]
+        offs = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            np.cumsum([len(b) for b in bs], out=offs[1:])
+        on_gpu = self._lib is _capi._lib            # (the test suite's CPU model of the device takes host tensors)
+        dev = torch.device("cuda", self._device) if on_gpu else torch.device("cpu")
+        text = torch.zeros(int(offs[-1]) + 32, dtype=torch.uint8)
+        if offs[-1]:
+            text[:int(offs[-1])] = torch.frombuffer(bytearray(b"".join(bs)), dtype=torch.uint8)
+        d_text, d_offs = text.to(dev)[:int(offs[-1])], torch.from_numpy(offs).to(dev)
+        d_ids, _, total = self.EncodeDevice(d_text, d_offs)
+        d_counts = self.CountIdsDevice(d_ids[:total])
+        return d_counts.cpu().numpy()
+
+    def GenerateVocabulary(self, in_paths, out_path):
+        """``spm_encode --generate_vocabulary`` (spm_encode_main.cc:102-109, :167-172): counts how often every piece is
+        emitted over the corpus file(s) ``in_paths`` (one path or a sequence; the counts accumulate over the files) and
+        writes ``piece TAB count`` lines to ``out_path``, by descending count and then by piece.  Unknown and control
+        pieces are left out.  ``SetEncodeExtraOptions`` and a vocabulary restriction apply.  Returns
+        ``(sentences, ids, lines)``."""
+        self._need()
+        self._apply(False, False, False)
+        if isinstance(in_paths, (str, bytes, os.PathLike)):
+            in_paths = [in_paths]
+        counts = np.zeros(self.GetPieceSize() + 1, dtype=np.uint64)
+        sentences = ids = 0
+        for path in in_paths:
+            ns, ni = C.c_uint64(0), C.c_uint64(0)
+            self._check(self._lib.spmx_count_file(self._h, os.fsencode(path), counts.ctypes.data, C.byref(ns), C.byref(ni)))
+            sentences += int(ns.value)
+            ids += int(ni.value)
+        nl = C.c_uint64(0)
+        self._check(self._lib.spmx_write_vocabulary(self._h, counts.ctypes.data, os.fsencode(out_path), C.byref(nl)))
+        return sentences, ids, int(nl.value)
+
     def SetProfiling(self, enabled):
         self._need()
         self._lib.spmx_set_profiling(self._h, 1 if enabled else 0)
