@@ -888,6 +888,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       expand * ws->reserve_text_bytes + (10 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * (ws->reserve_n > n ? ws->reserve_n : n) + 4096 +
       (direct ? (ws->reserve_text_bytes + (1 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * (ws->reserve_n > n ? ws->reserve_n : n)) / (ids16 ? 2 : 1) + 8 : 0);
   for (int attempt = 0; attempt < 4; ++attempt) {
+    uint64_t long_launches = 0;             // launches of the long form in this attempt (Profile::path[5])
     HIP_OR_RETURN(h, ws->d_arena.Reserve(arena_need > arena_reserve ? arena_need : arena_reserve));
     if (spans) HIP_OR_RETURN(h, ws->d_arena_tb.Reserve(ws->d_arena.cap));
     if (prof) HIP_OR_RETURN(h, hipEventRecord(ws->ev[kNumSlots][0], stream));
@@ -974,7 +975,11 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
     };
     // the long form over one device-side list (BPE), growing the slice pool until every sentence has had its turn
     // (uni: the wave-cooperative unigram form over the same pool, kernels_uniwave.h)
-    auto long_launch = [&](const uint32_t *list, const uint32_t *d_count, uint32_t count, bool uni = false) -> int {
+    // (segs: SEVERAL lists at once -- n_seg of them, seg_counts[k] entries each as the host read them back, `count` their
+    // sum: they are copied behind one another into the second retry list, which the first turn does not write, and the
+    // launches below see one list: one kernel, one pool, one retry list, one read-back, and kernels that know nothing of it)
+    auto long_launch = [&](const uint32_t *list, const uint32_t *d_count, uint32_t count, bool uni = false,
+                           const uint32_t *const *segs = nullptr, const uint32_t *seg_counts = nullptr, uint32_t n_seg = 0) -> int {
       if (count == 0) return kOk;
       LongArgs la{};
       la.dev = h->dev; if (h->uw_exact) la.dev.uw_f32_limit = 0.f; la.text = d_text; la.offs = d_offsets;
@@ -990,6 +995,14 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       if (want > (4ull << 30)) want = 4ull << 30;
       int turn = 0;
       uint32_t left = count;
+      if (n_seg) {
+        uint32_t at = 0;
+        for (uint32_t k = 0; k < n_seg; at += seg_counts[k++])
+          HIP_OR_RETURN(h, hipMemcpyAsync(retry_lists[1] + at, segs[k], seg_counts[k] * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        ws->h_ctrl->retry_count[1] = count;                        // (pinned: read when the copy runs; the first turn's read-back is retry_count[0])
+        HIP_OR_RETURN(h, hipMemcpyAsync(&ws->d_ctrl->retry_count[1], &ws->h_ctrl->retry_count[1], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        list = retry_lists[1]; d_count = &ws->d_ctrl->retry_count[1];
+      }
       for (int round = 0; round < 40 && left > 0; ++round) {
         HIP_OR_RETURN(h, ws->d_pool.Reserve(want));
         la.pool = ws->d_pool.p; la.pool_cap = ws->d_pool.cap;
@@ -1010,6 +1023,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
         else HIP_OR_RETURN(h, LaunchBpeLong(la, static_cast<int>(g), stream));
         HIP_OR_RETURN(h, record(kSlotLong, 1));
         ws->slot_used[kSlotLong] = true;
+        ++long_launches;
         HIP_OR_RETURN(h, hipMemcpyAsync(&ws->h_ctrl->pool_head, &ws->d_ctrl->pool_head, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
         HIP_OR_RETURN(h, hipMemcpyAsync(&ws->h_ctrl->retry_count[turn], &ws->d_ctrl->retry_count[turn], sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_OR_RETURN(h, hipStreamSynchronize(stream));
@@ -1080,11 +1094,19 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
           }
           const double est_wave_ms = 2.7e-7 * static_cast<double>(tail_vol), est_lane_ms = 4.5e-3 * static_cast<double>(rcap_max);
           const bool few = tail && (total < 4096 || est_wave_ms < est_lane_ms);
+          // (every class that takes this form in ONE launch: these are latency-bound launches of a sentence per wavefront --
+          // the headline's 500 handed-on sentences span two classes, 0.079 ms and a host round trip each)
+          const uint32_t *segs[kMaxClasses];
+          uint32_t seg_counts[kMaxClasses], n_seg = 0, seg_total = 0;
           for (int c = 0; c < ncls; ++c) {
             if (cnt[c] == 0 || !(uni_class[c] || few || (tail && cls[c].rcap > kMaxStagedRaw))) continue;
-            if (int rc = long_launch(lists + static_cast<size_t>(c) * n, &d_counts[c], cnt[c], true); rc != kOk) return rc;
+            segs[n_seg] = lists + static_cast<size_t>(c) * n;
+            seg_counts[n_seg++] = cnt[c];
+            seg_total += cnt[c];
             cnt[c] = 0;
           }
+          if (n_seg == 1) { if (int rc = long_launch(segs[0], d_counts + (segs[0] - lists) / n, seg_total, true); rc != kOk) return rc; }
+          else if (n_seg > 1) { if (int rc = long_launch(nullptr, nullptr, seg_total, true, segs, seg_counts, n_seg); rc != kOk) return rc; }
         }
         if (tail) return stream_launch(kSlotDoc, tail_qi, 0, ncls, cnt, false, 0);
         int c_doc = ncls;                    // first class of the document launch
@@ -1456,6 +1478,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       p.path[0] = ws->h_ctrl->side.n_backlog; p.path[1] = ws->h_ctrl->side.over_count; p.path[2] = ws->h_ctrl->side.long_count;
       p.path[3] = ws->h_ctrl->side.n_failed;
       p.path[4] = static_cast<uint64_t>(attempt);   // (encodes of the batch again with a larger arena)
+      p.path[5] = long_launches;
       HIP_OR_RETURN(h, hipEventElapsedTime(&p.total_ms, ws->ev[kNumSlots][0], ws->ev[kNumSlots][1]));
       std::lock_guard<std::mutex> l(h->mu);
       h->prof = p;
@@ -4380,7 +4403,7 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
     // L + 8 + 4 T' + 8 per sentence
     if (bytes) bytes[c] = p.raw_bytes[c] + 16 * p.sentences[c] + 4 * p.ids[c];
   }
-  if (path) for (int k = 0; k < 5; ++k) path[k] = p.path[k];
+  if (path) for (int k = 0; k < 6; ++k) path[k] = p.path[k];
   if (total_ms) *total_ms = p.total_ms;
   return p.n;
 }
