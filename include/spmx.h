@@ -412,6 +412,43 @@ int spmx_sample_encode_batch(spmx_handle *h, const char *text, const uint64_t *o
 int spmx_sample_encode_batch_spans(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, int nbest_size,
                                    float alpha, uint64_t seed, int32_t **ids, uint64_t **id_offsets, uint32_t **begin,
                                    uint32_t **end, uint32_t **nbegin, uint32_t **nend);
+/* ---- lattice scoring -------------------------------------------------------
+ * CalculateEntropy(input, alpha, float *) (src/sentencepiece_processor.h:385-386, .cc:748-759; Lattice::CalculateEntropy
+ * src/unigram_model.cc:263-291) per sentence, unigram models only (INTERNAL "CalculateEntropy is not available for the
+ * current model." otherwise): *entropy holds n floats, released with spmx_free().  The value is the REFERENCE's: its
+ * float recurrences in its order, which on long text lie far from the exact entropy.  An empty
+ * sentence gives -0.0, as the reference does.  No length limit. */
+int spmx_calculate_entropy_batch(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, float alpha,
+                                 float **entropy);
+/* SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, ...) (src/sentencepiece_processor.h:355-378,
+ * .cc:724-746; unigram::Model::SampleEncodeAndScore src/unigram_model.cc:741-846) per sentence, unigram models only
+ * (INTERNAL "SampleEncodeAndScore is not available for the current model." otherwise).  Results as
+ * spmx_nbest_encode_batch gives them.
+ *   wor = 0   num_samples segmentations drawn independently from the lattice (Lattice::Sample(alpha)), each with
+ *             score = log of its probability: the float sum of alpha * piece score minus the lattice's log Z.
+ *             Draw j of sentence i comes from a generator keyed by (seed, i, j) alone.
+ *   wor = 1   num_samples DISTINCT segmentations by Gumbel top-k (Lattice::NBest(num_samples + 1, true, alpha),
+ *             src/unigram_model.cc:391-450): the search's last result gives the threshold kappa and is dropped, and a
+ *             score is the log of the segmentation's inclusion probability (:811-826).  include_best puts the Viterbi
+ *             path first, with score 0.0, and takes it out of the samples (:775-793).  A lattice with P <= num_samples
+ *             paths gives P - 1 results, as the reference does.  The Gumbel variates come from a generator keyed by
+ *             (seed, sentence index).
+ * The seed goes through a 64-bit hash before it enters either key: seed and seed + 1 give unrelated draws, so callers
+ * may simply count up (the hosts do, for calls without a seed of their own).
+ * A sentence that is empty after normalization owns no result, nor does, without replacement, one whose lattice has a
+ * single path: the reference's per-sentence INTERNAL "SampleEncodeAndScore returns empty result." (.cc:735).  The call
+ * fails with that status where no sentence could own one: include_best without wor, num_samples < 1.  num_samples > 512 is refused with INTERNAL (the 0.2.1 sources
+ * have no cap). */
+int spmx_sample_encode_and_score_batch(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n,
+                                       int num_samples, float alpha, int wor, int include_best, uint64_t seed,
+                                       int32_t **ids, uint64_t **id_offsets, float **scores, uint64_t **result_offsets);
+/* ... with the four span arrays of spmx_nbest_encode_batch_spans. */
+int spmx_sample_encode_and_score_batch_spans(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n,
+                                             int num_samples, float alpha, int wor, int include_best, uint64_t seed,
+                                             int32_t **ids, uint64_t **id_offsets, float **scores,
+                                             uint64_t **result_offsets, uint32_t **begin, uint32_t **end,
+                                             uint32_t **nbegin, uint32_t **nend);
+
 /* The reference's ORIGINAL unigram encoder (EncoderVersion::kOriginal, src/unigram_model.cc:674-692): the lattice of
  * Lattice::SetSentence / Model::PopulateNodes and Lattice::Viterbi (:161-198, all-float, first best left node wins)
  * instead of EncodeOptimized.  Same ids except where float and double arithmetic break a tie differently. */

@@ -106,6 +106,17 @@ struct SentencePieceText {
 // NBestSentencePieceText (src/sentencepiece.proto): the results of NBestEncode, best first
 struct NBestSentencePieceText {
   std::vector<SentencePieceText> nbests;
+  // nbests = 1, repeated (src/sentencepiece.proto:67-69)
+  std::string SerializeAsString() const {
+    std::string out;
+    for (const SentencePieceText &t : nbests) {
+      const std::string m = t.SerializeAsString();
+      out.push_back(static_cast<char>(1 << 3 | 2));
+      for (uint64_t v = m.size();;) { if (v >= 0x80) { out.push_back(static_cast<char>(v | 0x80)); v >>= 7; } else { out.push_back(static_cast<char>(v)); break; } }
+      out.append(m);
+    }
+    return out;
+  }
 };
 
 // An encoded batch as the library hands it over: the CSR arrays themselves (pinned host memory for big batches), owned
@@ -579,6 +590,140 @@ class SentencePieceProcessor {
     return pieces;
   }
 
+  // ---- lattice scoring (sentencepiece_processor.h:355-386, .cc:724-759; unigram models).  CalculateEntropy gives the
+  // reference's float number.  SampleEncodeAndScore: num_samples segmentations with the log of their
+  // probability (wor false) or of their inclusion probability (wor true, distinct segmentations; include_best puts the
+  // best one first with score 0); a call without a seed of its own takes the next value of a per-process counter ----
+  virtual util::Status CalculateEntropy(std::string_view input, float alpha, float *entropy) const {
+    if (!h_) return status();
+    if (!entropy) return util::Status(util::StatusCode::kInternal, "output container is null");
+    const uint64_t offs[2] = {0, input.size()};
+    float *e = nullptr;
+    const int rc = spmx_calculate_entropy_batch(h_, input.data() ? input.data() : "", offs, 1, alpha, &e);
+    if (rc == 0) *entropy = e[0];
+    spmx_free(e);
+    return FromHandle(rc);
+  }
+  virtual float CalculateEntropy(std::string_view input, float alpha) const {   // errors are swallowed
+    float e = 0.f;
+    (void)CalculateEntropy(input, alpha, &e);
+    return e;
+  }
+  // batch form: one float per sentence
+  util::Status CalculateEntropyBatchFlat(const char *text, const uint64_t *offsets, uint64_t n, float alpha, std::vector<float> *entropy) const {
+    if (!h_) return status();
+    if (!entropy) return util::Status(util::StatusCode::kInternal, "output container is null");
+    float *e = nullptr;
+    const int rc = spmx_calculate_entropy_batch(h_, text, offsets, n, alpha, &e);
+    if (rc == 0) entropy->assign(e, e + n);
+    spmx_free(e);
+    return FromHandle(rc);
+  }
+  virtual util::Status SampleEncodeAndScore(std::string_view input, int num_samples, float alpha, bool wor, bool include_best,
+                                            std::vector<std::pair<std::vector<int>, float>> *ids) const {
+    return SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, NextScoreSeed(), ids);
+  }
+  util::Status SampleEncodeAndScore(std::string_view input, int num_samples, float alpha, bool wor, bool include_best, uint64_t seed,
+                                    std::vector<std::pair<std::vector<int>, float>> *ids) const {
+    if (!h_) return status();
+    if (!ids) return util::Status(util::StatusCode::kInternal, "output container is null");
+    ids->clear();
+    const uint64_t offs[2] = {0, input.size()};
+    int32_t *i = nullptr;
+    uint64_t *io = nullptr, *ro = nullptr;
+    float *sc = nullptr;
+    int rc = spmx_sample_encode_and_score_batch(h_, input.data() ? input.data() : "", offs, 1, num_samples, alpha, wor, include_best,
+                                                seed, &i, &io, &sc, &ro);
+    if (rc == 0)
+      for (uint64_t r = ro[0]; r < ro[1]; ++r) ids->emplace_back(std::vector<int>(i + io[r], i + io[r + 1]), sc[r]);
+    spmx_free(i); spmx_free(io); spmx_free(sc); spmx_free(ro);
+    if (rc == 0 && ids->empty()) return util::Status(util::StatusCode::kInternal, "SampleEncodeAndScore returns empty result.");   // .cc:735
+    return FromHandle(rc);
+  }
+  virtual util::Status SampleEncodeAndScore(std::string_view input, int num_samples, float alpha, bool wor, bool include_best,
+                                            NBestSentencePieceText *samples_spt) const {
+    return SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, NextScoreSeed(), samples_spt);
+  }
+  util::Status SampleEncodeAndScore(std::string_view input, int num_samples, float alpha, bool wor, bool include_best, uint64_t seed,
+                                    NBestSentencePieceText *samples_spt) const {
+    if (!h_) return status();
+    if (!samples_spt) return util::Status(util::StatusCode::kInternal, "output proto is null");
+    samples_spt->nbests.clear();
+    const uint64_t offs[2] = {0, input.size()};
+    int32_t *ids = nullptr;
+    uint64_t *io = nullptr, *ro = nullptr, *no = nullptr;
+    float *sc = nullptr;
+    uint32_t *b = nullptr, *e = nullptr, *nb = nullptr, *ne = nullptr;
+    char *norm = nullptr;
+    const char *txt = input.data() ? input.data() : "";
+    int rc = spmx_sample_encode_and_score_batch_spans(h_, txt, offs, 1, num_samples, alpha, wor, include_best, seed, &ids, &io, &sc,
+                                                      &ro, &b, &e, &nb, &ne);
+    if (rc == 0) rc = spmx_normalize_batch(h_, txt, offs, 1, &norm, &no, nullptr);
+    if (rc == 0) {
+      for (uint64_t r = ro[0]; r < ro[1]; ++r) {
+        samples_spt->nbests.emplace_back();
+        samples_spt->nbests.back().score = sc[r];
+        samples_spt->nbests.back().has_score = true;
+        FillPieces(input, norm, ids, b, e, nb, ne, io[r], io[r + 1], &samples_spt->nbests.back());
+      }
+    }
+    spmx_free(ids); spmx_free(io); spmx_free(sc); spmx_free(ro); spmx_free(b); spmx_free(e); spmx_free(nb); spmx_free(ne);
+    spmx_free(norm); spmx_free(no);
+    if (rc == 0 && samples_spt->nbests.empty()) return util::Status(util::StatusCode::kInternal, "SampleEncodeAndScore returns empty result.");
+    return FromHandle(rc);
+  }
+  virtual util::Status SampleEncodeAndScore(std::string_view input, int num_samples, float alpha, bool wor, bool include_best,
+                                            std::vector<std::pair<std::vector<std::string>, float>> *pieces) const {
+    if (!h_) return status();
+    if (!pieces) return util::Status(util::StatusCode::kInternal, "output container is null");
+    pieces->clear();
+    NBestSentencePieceText nb;
+    const util::Status st = SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, &nb);
+    if (!st.ok()) return st;
+    for (auto &spt : nb.nbests) {
+      pieces->emplace_back(std::vector<std::string>(), spt.score);
+      for (auto &p : spt.pieces) pieces->back().first.push_back(std::move(p.piece));
+    }
+    return util::Status();
+  }
+  std::vector<std::pair<std::vector<int>, float>> SampleEncodeAndScoreAsIds(std::string_view input, int num_samples, float alpha, bool wor,
+                                                                            bool include_best) const {   // errors are swallowed
+    std::vector<std::pair<std::vector<int>, float>> ids;
+    (void)SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, &ids);
+    return ids;
+  }
+  std::vector<std::pair<std::vector<std::string>, float>> SampleEncodeAndScoreAsPieces(std::string_view input, int num_samples, float alpha,
+                                                                                       bool wor, bool include_best) const {
+    std::vector<std::pair<std::vector<std::string>, float>> pieces;
+    (void)SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, &pieces);
+    return pieces;
+  }
+  virtual std::string SampleEncodeAndScoreAsSerializedProto(std::string_view input, int num_samples, float alpha, bool wor,
+                                                            bool include_best) const {
+    NBestSentencePieceText nb;
+    (void)SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, &nb);
+    return nb.SerializeAsString();
+  }
+  // batch form: the CSR of results as spmx_sample_encode_and_score_batch gives it; draw j of sentence i is keyed by (seed, i, j)
+  util::Status SampleEncodeAndScoreBatchFlat(const char *text, const uint64_t *offsets, uint64_t n, int num_samples, float alpha, bool wor,
+                                             bool include_best, uint64_t seed, std::vector<int32_t> *ids, std::vector<uint64_t> *id_offsets,
+                                             std::vector<float> *scores, std::vector<uint64_t> *result_offsets) const {
+    if (!h_) return status();
+    if (!ids || !id_offsets || !scores || !result_offsets) return util::Status(util::StatusCode::kInternal, "output container is null");
+    int32_t *i = nullptr;
+    uint64_t *io = nullptr, *ro = nullptr;
+    float *sc = nullptr;
+    const int rc = spmx_sample_encode_and_score_batch(h_, text, offsets, n, num_samples, alpha, wor, include_best, seed, &i, &io, &sc, &ro);
+    if (rc == 0) {
+      result_offsets->assign(ro, ro + n + 1);
+      id_offsets->assign(io, io + ro[n] + 1);
+      scores->assign(sc, sc + ro[n]);
+      ids->assign(i, i + io[ro[n]]);
+    }
+    spmx_free(i); spmx_free(io); spmx_free(sc); spmx_free(ro);
+    return FromHandle(rc);
+  }
+
   // ---- sampling (sentencepiece_processor.h:346-353, .cc:678-720): lattice sampling / n-best sampling (unigram),
   // BPE-dropout (BPE).  The draws are keyed by (seed, sentence); each call without a seed of its own takes the next
   // value of a per-process counter, so repeated calls draw afresh as the reference's thread-local generator does ----
@@ -909,6 +1054,10 @@ class SentencePieceProcessor {
     if (rc == 0) return util::Status();
     h_ = nullptr;
     return util::Status(static_cast<util::StatusCode>(rc), spmx_last_error(nullptr));
+  }
+  static uint64_t NextScoreSeed() {
+    static std::atomic<uint64_t> calls{std::random_device{}()};   // (as SampleEncode's counter)
+    return ++calls;
   }
   util::Status FromHandle(int rc) const {
     if (rc == 0) return util::Status();

@@ -2553,13 +2553,18 @@ int spmx_encode_batch_spans_device(spmx_handle *h, const void *d_text, uint64_t 
 
 namespace {
 // The lattice kernels (kernels_nbest.h), host-buffer form.  mode 0: NBestEncode; 1: Lattice::Sample(inv_theta); 2: the
-// kOriginal encoder (Lattice::Viterbi).  Modes 1 and 2 give one result per sentence.
+// kOriginal encoder (Lattice::Viterbi); 3: Lattice::CalculateEntropy(inv_theta) -- one result without ids per sentence,
+// its score the entropy; 4: SampleEncodeAndScore with replacement -- nbest_size draws per sentence (none for a sentence that
+// is empty after normalization), each with its log probability; 5: SampleEncodeAndScore without replacement -- nbest_size
+// is num_samples + 2, the rows a sentence may fill while the kernel works (the best path under include_best and the
+// num_samples + 1 results of the search), of which at most num_samples (+ 1) remain.  Modes 1, 2 and 3 give one result per
+// sentence.
 // begin / end / nbegin / nend (all or none): the spans form -- per id of every result the byte range of the input and of
 // the normalized text its token covers, as spmx_encode_batch_spans gives them for the best path.
 int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, int mode, int nbest_size,
                      float inv_theta, uint64_t seed, int32_t **ids, uint64_t **id_offsets, float **scores,
                      uint64_t **result_offsets, uint32_t **begin = nullptr, uint32_t **end = nullptr,
-                     uint32_t **nbegin = nullptr, uint32_t **nend = nullptr) {
+                     uint32_t **nbegin = nullptr, uint32_t **nend = nullptr, int include_best = 0) {
   if (!ids || !id_offsets || !scores || !result_offsets) return Fail(h, kInternal, "output container is null");
   *ids = nullptr; *id_offsets = nullptr; *scores = nullptr; *result_offsets = nullptr;
   const bool spans = begin != nullptr;
@@ -2567,10 +2572,13 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
   if (spans) { *begin = nullptr; *end = nullptr; *nbegin = nullptr; *nend = nullptr; }
   if (h->model.model_type != kUnigram)
     return Fail(h, kInternal, mode == 0 ? "NBestEncode is not available for the current model."     // sentencepiece_processor.cc:662
+                            : mode == 3 ? "CalculateEntropy is not available for the current model."   // :752
+                            : mode >= 4 ? "SampleEncodeAndScore is not available for the current model."   // :728
                                         : "SampleEncode is not available for the current model.");  // :690
+  const char *what = mode == 3 ? "CalculateEntropy" : mode >= 4 ? "SampleEncodeAndScore" : "NBestEncode";   // (modes 0 to 2 keep the text they had)
   if (nbest_size > 1024) nbest_size = 1024;                                              // unigram_model.cc:692
   if (nbest_size < 1) nbest_size = 1;
-  if (mode != 0) nbest_size = 1;
+  if (mode != 0 && mode < 4) nbest_size = 1;
   {
     if ((mode == 0 && nbest_size == 1) || n == 0) {          // :694-696 the plain encoder, score 0.0; one result per sentence
       int32_t *i1 = nullptr;
@@ -2625,7 +2633,7 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
     if (n * K + 1 > (1ull << 32)) return Fail(h, kInvalidArgument, "too many results for one batch");
     NBestArgs a{};
     a.dev = h->dev; a.norm = ws->d_norm.p; a.norm_offs = ws->d_id_offs.p; a.n = static_cast<uint32_t>(n); a.nbest = K;
-    a.mode = static_cast<uint32_t>(mode); a.inv_theta = inv_theta; a.seed = seed;
+    a.mode = static_cast<uint32_t>(mode); a.inv_theta = inv_theta; a.seed = seed; a.include_best = include_best ? 1u : 0u;
     const uint64_t hyps0 = static_cast<uint64_t>(K) * 512;   // (a C2 sentence's n-best 5 makes ~1,000; what outgrows the slice runs again)
     // The first launch's capacities follow the batch: a slice sized for 1024 bytes and 16384 nodes is 0.7 MB a lane, of
     // which a 126-byte sentence touches a twentieth, and the lanes in flight are what the budget holds (200 k sentences,
@@ -2638,7 +2646,8 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
     uint64_t nodes0 = (len0 + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
     if (nodes0 > kNbMaxNodes) nodes0 = kNbMaxNodes;
     const uint64_t hyps_min = h->nbest_hyps_min;
-    const uint32_t max_hyps0 = mode != 0 ? 512u : static_cast<uint32_t>(hyps0 < hyps_min ? hyps_min : (hyps0 > 262144 ? 262144 : hyps0));
+    // (modes 1 and 4 keep alpha there, len0 + 1 floats of the 2048; mode 3 alpha and H, 2050 floats at 1024 bytes)
+    const uint32_t max_hyps0 = mode == 3 ? static_cast<uint32_t>(len0 / 2 + 2) : (mode != 0 && mode != 5) ? 512u : static_cast<uint32_t>(hyps0 < hyps_min ? hyps_min : (hyps0 > 262144 ? 262144 : hyps0));
     const uint64_t budget = h->nbest_budget;                  // HBM for the lanes' slices
     HIP_OR_RETURN(h, ws->d_res_off.Reserve(n * K + 1));
     HIP_OR_RETURN(h, ws->d_span_begin.Reserve(n * K + 1));     // result lengths
@@ -2680,7 +2689,7 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
         // and one UNK node.
         const uint64_t L = ws->h_ctrl->side.over_max_raw > kNbMaxLen ? ws->h_ctrl->side.over_max_raw : kNbMaxLen;
         const uint64_t nodes = (L + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
-        uint64_t hy = mode != 0 ? L / 4 + 512 : (static_cast<uint64_t>(K) * (L + 2) * 4 + 16384) * hy_scale;   // mode 1: alpha[L + 1] floats
+        uint64_t hy = mode == 3 ? L / 2 + 512 : (mode != 0 && mode != 5) ? L / 4 + 512 : (static_cast<uint64_t>(K) * (L + 2) * 4 + 16384) * hy_scale;   // modes 1, 4: alpha[L + 1] floats; mode 3: H[L + 1] too
         if (hy < max_hyps0 * hy_scale) hy = max_hyps0 * hy_scale;
         if (L >= (1ull << 31) || nodes >= (1ull << 32) || hy >= (1ull << 32)) return Fail(h, kOutOfRange, "a sentence is too long for the lattice");
         a.max_len = static_cast<uint32_t>(L); a.max_nodes = static_cast<uint32_t>(nodes); a.max_hyps = static_cast<uint32_t>(hy);
@@ -2707,10 +2716,10 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
         HIP_OR_RETURN(h, hipStreamSynchronize(st));
         hy_scale *= 4;
         if (round == 9 && ws->h_ctrl->retry_count[(round + 1) & 1])
-          return Fail(h, kResourceExhausted, "NBestEncode: the agenda of a sentence exceeds the device capacities");
+          return Fail(h, kResourceExhausted, std::string(what) + ": the agenda of a sentence exceeds the device capacities");
       }
       const uint32_t stw = ws->h_ctrl->status;
-      if (stw & kStNbestOverflow) return Fail(h, kResourceExhausted, "NBestEncode: the agenda of a sentence exceeds the device capacities");
+      if (stw & kStNbestOverflow) return Fail(h, kResourceExhausted, std::string(what) + ": the agenda of a sentence exceeds the device capacities");
       // (a lane stops at its first result that does not fit, so arena_head is a lower bound: grow geometrically)
       if (stw & kStArenaOverflow) { arena_need = 4 * ws->d_arena.cap > ws->h_ctrl->arena_head + 1024 ? 4 * ws->d_arena.cap : ws->h_ctrl->arena_head + 1024; continue; }
       // results -> host CSR.  The result arrays land in ONE pinned staging block (the workspace's h_text, idle in this
@@ -2888,6 +2897,71 @@ int spmx_encode_batch_original(spmx_handle *h, const char *text, const uint64_t 
     free(ro);
     return rc;
   });
+}
+
+// CalculateEntropy(input, alpha, &entropy) (src/sentencepiece_processor.cc:748-759; Lattice::CalculateEntropy
+// src/unigram_model.cc:263-291) per sentence: the reference's float recurrences in its order (kernels_nbest.h mode 3).
+int spmx_calculate_entropy_batch(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, float alpha,
+                                 float **entropy) {
+  if (!h) return kInvalidArgument;
+  if (!entropy) return Fail(h, kInternal, "output container is null");
+  return Guard(h, [&]() -> int {
+    *entropy = nullptr;
+    int32_t *ids = nullptr;
+    uint64_t *io = nullptr, *ro = nullptr;
+    float *sc = nullptr;
+    const int rc = LatticeBatchHost(h, text, offsets, n, 3, 1, alpha, 0, &ids, &io, &sc, &ro);
+    if (rc != kOk) return rc;
+    const bool one_each = ro[n] == n;                  // (one result per sentence, in order)
+    spmx_free(ids); spmx_free(io); spmx_free(ro);
+    if (!one_each) { spmx_free(sc); return Fail(h, kInternal, "CalculateEntropy: a sentence without a result"); }
+    *entropy = sc;
+    return kOk;
+  });
+}
+
+// SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, NBestSentencePieceText *)
+// (src/sentencepiece_processor.cc:724-746; unigram::Model::SampleEncodeAndScore src/unigram_model.cc:741-846) per
+// sentence.  A sentence for which the reference returns "SampleEncodeAndScore returns empty result." (:735) owns no
+// result; the call itself fails with that status where no sentence can have one.
+namespace {
+int SampleEncodeAndScoreImpl(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, int num_samples,
+                             float alpha, int wor, int include_best, uint64_t seed, int32_t **ids, uint64_t **id_offsets,
+                             float **scores, uint64_t **result_offsets, uint32_t **begin, uint32_t **end,
+                             uint32_t **nbegin, uint32_t **nend) {
+  if (!h) return kInvalidArgument;
+  if (!ids || !id_offsets || !scores || !result_offsets) return Fail(h, kInternal, "output container is null");
+  const bool spans = begin != nullptr;
+  if (spans && (!end || !nbegin || !nend)) return Fail(h, kInternal, "output container is null");
+  return Guard(h, [&]() -> int {
+    *ids = nullptr; *id_offsets = nullptr; *scores = nullptr; *result_offsets = nullptr;
+    if (spans) { *begin = nullptr; *end = nullptr; *nbegin = nullptr; *nend = nullptr; }
+    if (h->model.model_type != kUnigram)
+      return Fail(h, kInternal, "SampleEncodeAndScore is not available for the current model.");   // :727-728
+    // include_best without wor: "include_best not supported for wor false" is logged and nothing returned
+    // (unigram_model.cc:757-760); num_samples < 1: the loop of :829 never runs, and without replacement nothing is left
+    // once the last of num_samples + 1 results is dropped (:796-798)
+    if ((include_best && !wor) || num_samples < 1) return Fail(h, kInternal, "SampleEncodeAndScore returns empty result.");
+    if (num_samples > 512) return Fail(h, kInternal, "num_samples must be num_samples <= 512");
+    return LatticeBatchHost(h, text, offsets, n, wor ? 5 : 4, wor ? num_samples + 2 : num_samples, alpha, seed, ids, id_offsets,
+                            scores, result_offsets, begin, end, nbegin, nend, include_best);
+  });
+}
+}  // namespace
+int spmx_sample_encode_and_score_batch(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n,
+                                       int num_samples, float alpha, int wor, int include_best, uint64_t seed,
+                                       int32_t **ids, uint64_t **id_offsets, float **scores, uint64_t **result_offsets) {
+  return SampleEncodeAndScoreImpl(h, text, offsets, n, num_samples, alpha, wor, include_best, seed, ids, id_offsets, scores,
+                                  result_offsets, nullptr, nullptr, nullptr, nullptr);
+}
+int spmx_sample_encode_and_score_batch_spans(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n,
+                                             int num_samples, float alpha, int wor, int include_best, uint64_t seed,
+                                             int32_t **ids, uint64_t **id_offsets, float **scores,
+                                             uint64_t **result_offsets, uint32_t **begin, uint32_t **end,
+                                             uint32_t **nbegin, uint32_t **nend) {
+  if (h && (!begin || !end || !nbegin || !nend)) return Fail(h, kInternal, "output container is null");
+  return SampleEncodeAndScoreImpl(h, text, offsets, n, num_samples, alpha, wor, include_best, seed, ids, id_offsets, scores,
+                                  result_offsets, begin, end, nbegin, nend);
 }
 
 // SampleEncode(input, nbest_size, alpha, &ids) (src/sentencepiece_processor.cc:678-720) per sentence:

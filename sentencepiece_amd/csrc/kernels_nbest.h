@@ -34,7 +34,7 @@ SPMX_HD inline uint64_t NbestLaneBytes(uint64_t max_len, uint64_t max_nodes, uin
        + NbAlign16((max_len + 3) * 4ull)                     // end_off: CSR offsets of the nodes ending at a position
        + NbAlign16(max_nodes * ix)                           // end_idx
        + NbAlign16((max_len + 2) * ix)                       // cursor per position
-       + NbAlign16(max_hyps * sizeof(NbHyp))                 // hypotheses (mode 1: alpha, one float per position)
+       + NbAlign16(max_hyps * sizeof(NbHyp))                 // hypotheses (modes 1 and 4: alpha, one float per position; mode 3: alpha and H)
        + kNbAgendaCap * 4ull + 64;
 }
 
@@ -43,11 +43,17 @@ struct NBestArgs {
   const uint8_t *norm;          // packed normalized text, device form
   const uint64_t *norm_offs;    // n + 1
   uint32_t n;
-  uint32_t nbest;               // 2 .. 1024 (mode 0); 1 otherwise
+  uint32_t nbest;               // 2 .. 1024 (mode 0); the draws per sentence, 1 .. 512 (mode 4); the rows a sentence may fill,
+                                // num_samples + 2 (mode 5: the best path and the num_samples + 1 results of the search); 1 otherwise
   uint32_t mode;                // 0 Lattice::NBest (:345-515); 1 Lattice::Sample(inv_theta) (:511-542); 2 Lattice::Viterbi
-                                // (:161-198), the kOriginal encoder (:674-692)
-  float inv_theta;              // mode 1
-  uint64_t seed;                // mode 1: the lanes' generators are keyed by (seed, sentence index)
+                                // (:161-198), the kOriginal encoder (:674-692); 3 Lattice::CalculateEntropy(inv_theta)
+                                // (:263-291): one result without ids, its score the entropy; 4 SampleEncodeAndScore with
+                                // replacement (:828-843): `nbest` draws of mode 1's sampler, each with its log probability;
+                                // 5 SampleEncodeAndScore without replacement (:771-827): mode 0's A* with Gumbel keys
+  uint32_t include_best;        // mode 5: the Viterbi path first, with score 0, and out of the samples
+  float inv_theta;              // modes 1, 3, 4, 5
+  uint64_t seed;                // mode 1: the lanes' generators are keyed by (seed, sentence index); mode 4: draw j of
+                                // sentence i by (hash of the seed, i, j); mode 5: (hash of the seed, sentence index)
   uint8_t *scratch;             // [lanes of the launch][lane_bytes]
   uint64_t lane_bytes;
   uint32_t max_hyps;
@@ -113,6 +119,18 @@ SPMX_DEVICE uint32_t nb_heap_pop(uint32_t *heap, uint32_t *hn, const NbHyp *hy) 
   return top;
 }
 
+// std::exp(float) as the reference's build has it: glibc's expf.  The emulated body (tests/emu) runs on the host and calls
+// it, which is what makes its entropies the reference's bit for bit; the device takes the double exp rounded to float --
+// the same number but for a rare last bit (over the golden sentences the two forms differ in 2 results of 260, by
+// 5.6e-7 relative at most).
+SPMX_DEVICE float nb_exp_float(float x) {
+#ifdef SPMX_EMULATED
+  return expf(x);
+#else
+  return static_cast<float>(exp(static_cast<double>(x)));
+#endif
+}
+
 template <typename IX>
 SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
   typedef NbNodeT<IX> NbNode;
@@ -148,6 +166,14 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     }
     return dst + d.n_prefix;
   };
+  if (size == 0 && a.mode == 3u) {               // BOS and EOS alone: H[eos] = 0 + exp(0) * (0 + 0), returned negated (:263-291)
+    res_off[0] = 0;
+    res_len[0] = 0;
+    res_score[0] = -0.f;
+    a.res_count[s] = 1;
+    return;
+  }
+  if (size == 0 && (a.mode == 4u || a.mode == 5u)) return;         // :745-747 no result (the caller's "returns empty result.")
   if (size == 0) {                               // unigram_model.cc:688-690: one empty result, score 0
     int32_t *dst = alloc(n_extra);
     if (dst) put_extras(dst, 0);
@@ -241,7 +267,7 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     }
     return best;
   };
-  if (a.mode != 1u) {
+  if (a.mode == 0u || a.mode == 2u || (a.mode == 5u && a.include_best)) {
     for (uint32_t i = 2; i < n_nodes; ++i) nodes[i].backtrace = best_into(nodes[i].pos, nodes[i].score, &nodes[i].prev);
     nodes[1].backtrace = best_into(len, 0.f, &nodes[1].prev);
   }
@@ -311,36 +337,36 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     emit_path([&] { return nxt; }, [&](uint32_t h) { return nodes[h].prev; }, [&](uint32_t h) { return h == 1u; }, nodes[1].backtrace);
     return;
   }
-  if (a.mode == 1u) {
-    // ---- Lattice::Sample(inv_theta) (:511-542): ForwardAlgorithm (:200-216) -- alpha of a node depends on its begin
-    // position only: kept per position in the (idle) hypothesis slice -- then one left node after another from EOS,
-    // each drawn with probability exp(alpha[l] + inv_theta * score[l] - Z) (std::discrete_distribution's weights) ----
-    float *alpha = reinterpret_cast<float *>(hy);
-    auto lse = [](float x, float y, bool init) -> float {                   // LogSumExp (:47-59)
-      if (init) return y;
-      const float vmin = x < y ? x : y, vmax = x < y ? y : x;
-      if (vmax > vmin + 50.f) return vmax;
-      return static_cast<float>(static_cast<double>(vmax) + log(exp(static_cast<double>(vmin - vmax)) + 1.0));
-    };
-    alpha[0] = 0.f;
-    for (int pos = 1; pos <= len; ++pos) {
-      float acc = 0.f;
-      for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
-        const NbNode &ln = nodes[end_idx[l]];
-        acc = lse(acc, a.inv_theta * ln.score + alpha[ln.pos], l == end_off[pos]);
-      }
-      alpha[pos] = acc;
-    }
-    // a generator per sentence: splitmix64 over (seed, sentence); 53 random bits per draw
-    unsigned long long st = a.seed * 0x9E3779B97F4A7C15ull + (static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull;
-    auto uniform = [&]() -> double {
-      st += 0x9E3779B97F4A7C15ull;
-      unsigned long long z = st;
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      z ^= z >> 31;
-      return static_cast<double>(z >> 11) * (1.0 / 9007199254740992.0);
-    };
+  auto lse = [](float x, float y, bool init) -> float {                     // LogSumExp (:47-59)
+    if (init) return y;
+    const float vmin = x < y ? x : y, vmax = x < y ? y : x;
+    if (vmax > vmin + 50.f) return vmax;
+    return static_cast<float>(static_cast<double>(vmax) + log(exp(static_cast<double>(vmin - vmax)) + 1.0));
+  };
+  // a generator per sentence (mode 1) or per draw (mode 4), its state set by the mode: splitmix64, 53 random bits per draw
+  unsigned long long st = 0;
+  auto uniform = [&]() -> double {
+    st += 0x9E3779B97F4A7C15ull;
+    unsigned long long z = st;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return static_cast<double>(z >> 11) * (1.0 / 9007199254740992.0);
+  };
+  // The scored modes (4, 5) put the caller's seed through splitmix64's finalizer before it enters the key: calls without a
+  // seed of their own count one up per call, and the multiplier mode 1 gives the seed is the generator's own step, so
+  // under mode 1's key the stream of seed + 1 is that of seed moved on by one draw.  Mode 1 keeps its key: its draws
+  // are pinned.
+  auto hashed_seed = [&]() -> unsigned long long {
+    unsigned long long z = a.seed + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+  };
+  // Lattice::Sample's backward pass (:520-542) over the forward scores `alpha` (per begin position): one left node after
+  // another from EOS, each drawn with probability exp(alpha[l] + inv_theta * score[l] - Z) (std::discrete_distribution's
+  // weights).  Returns the path's first node; the chain runs left to right through `prev`, up to EOS (node 1).
+  auto draw_path = [&](const float *alpha) -> uint32_t {
     float Z = alpha[len];
     uint32_t nxt = 1u;                                  // the chain is built right to left: prev = the node to the right
     int pos = len;
@@ -363,36 +389,194 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
       pos = nodes[pick].pos;
       Z = alpha[pos];
     }
-    emit_path([&] { return nxt; }, [&](uint32_t h) { return nodes[h].prev; }, [&](uint32_t h) { return h == 1u; }, 0.f);
+    return nxt;
+  };
+  if (a.mode == 1u) {
+    // ---- Lattice::Sample(inv_theta) (:511-542): ForwardAlgorithm (:200-216) -- alpha of a node depends on its begin
+    // position only: kept per position in the (idle) hypothesis slice -- then the backward pass ----
+    float *alpha = reinterpret_cast<float *>(hy);
+    alpha[0] = 0.f;
+    for (int pos = 1; pos <= len; ++pos) {
+      float acc = 0.f;
+      for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
+        const NbNode &ln = nodes[end_idx[l]];
+        acc = lse(acc, a.inv_theta * ln.score + alpha[ln.pos], l == end_off[pos]);
+      }
+      alpha[pos] = acc;
+    }
+    // keyed by (seed, sentence)
+    st = a.seed * 0x9E3779B97F4A7C15ull + (static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull;
+    const uint32_t first = draw_path(alpha);
+    emit_path([&] { return first; }, [&](uint32_t h) { return nodes[h].prev; }, [&](uint32_t h) { return h == 1u; }, 0.f);
     return;
   }
-  // ---- A* (:375-515) ----
-  uint32_t n_hyp = 0, hn = 0;
-  hy[0] = NbHyp{0xFFFFFFFFu, 1u, nodes[1].backtrace, 0.f};
-  n_hyp = 1;
-  nb_heap_push(heap, &hn, hy, 0);
-  uint32_t n_res = 0;
+  if (a.mode == 3u || a.mode == 4u) {
+    // ---- The scoring entry points.  Their results are compared with the reference's NUMBER, which on long text is far
+    // from the exact one: the reference's recurrences in its order, in float, every product and sum
+    // rounded on its own as its x86-64 build rounds them -- the library is built with -ffp-contract=off throughout (csrc/
+    // Makefile), and the pragma in the scored blocks says so again where the result depends on it -- LogSumExp in
+    // double as written there, and std::exp(float) as nb_exp_float has it. ----
+#pragma clang fp contract(off)
+    float *alpha = reinterpret_cast<float *>(hy);
+    float *H = alpha + (len + 1);                       // mode 3 only
+    const uint64_t room = static_cast<uint64_t>(a.max_hyps) * (sizeof(NbHyp) / sizeof(float));
+    if ((a.mode == 3u ? 2ull : 1ull) * (static_cast<uint64_t>(len) + 1ull) > room) { set_aside(); return; }
+    alpha[0] = 0.f;                                     // ForwardAlgorithm (:200-216)
+    for (int pos = 1; pos <= len; ++pos) {
+      float acc = 0.f;
+      for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
+        const NbNode &ln = nodes[end_idx[l]];
+        const float w = a.inv_theta * ln.score;
+        acc = lse(acc, w + alpha[ln.pos], l == end_off[pos]);
+      }
+      alpha[pos] = acc;
+    }
+    if (a.mode == 3u) {
+      // Lattice::CalculateEntropy (:263-291): H of a node depends on its begin position only, as alpha does
+      H[0] = 0.f;
+      for (int pos = 1; pos <= len; ++pos) {
+        const float ar = alpha[pos];
+        float hsum = 0.f;
+        for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
+          const NbNode &ln = nodes[end_idx[l]];
+          const float w = a.inv_theta * ln.score;
+          const float t = w + alpha[ln.pos];
+          const float lp = t - ar;                      // log of the transition probability
+          const float e = nb_exp_float(lp);
+          const float g = H[ln.pos] + lp;
+          const float c = e * g;
+          hsum = hsum + c;
+        }
+        H[pos] = hsum;
+      }
+      res_off[0] = 0;
+      res_len[0] = 0;
+      res_score[0] = -H[len];
+      a.res_count[s] = 1;
+      return;
+    }
+    // with replacement (:828-843): the lattice and alpha once, then `nbest` draws, draw j from the generator keyed by
+    // (hashed seed, sentence, j) -- a third multiplier beside mode 1's, so the draws of (i, j) and (i + 1, j - 1) are unrelated
+    const float marginal = alpha[len];
+    const unsigned long long hs = hashed_seed();
+    for (uint32_t j = 0; j < a.nbest; ++j) {
+      st = hs + (static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull +
+           (static_cast<unsigned long long>(j) + 1ull) * 0xA0761D6478BD642Full;
+      const uint32_t first = draw_path(alpha);
+      float score = 0.f;
+      for (uint32_t h = first; h != 1u; h = nodes[h].prev) {
+        const float w = a.inv_theta * nodes[h].score;
+        score = score + w;
+      }
+      if (!emit_path([&] { return first; }, [&](uint32_t h) { return nodes[h].prev; }, [&](uint32_t h) { return h == 1u; }, score - marginal)) return;
+    }
+    return;
+  }
+  // ---- A* (:375-515).  Mode 5 is the same search with stochastic keys (NBest(samples + 1, true, inv_theta), :391-450):
+  // f(eos) is a Gumbel variate, a child's g is its log probability and its f a truncated Gumbel below its parent's ----
+  const bool wor = a.mode == 5u;
+  const uint32_t base = wor && a.include_best ? 1u : 0u;       // mode 5: row 0 is the best path (:756-769)
+  const uint32_t want = wor ? a.nbest - 1u : a.nbest;          // results of the search (mode 5: samples + 1; nbest = samples + 2 rows)
+  constexpr uint32_t kNone = 0xFFFFFFFFu;
+  uint32_t n_hyp = 0, hn = 0, n_res = 0;
+  // ids of the complete path below hypothesis `top`, left to right (PopulateSentencePieceText :581-613), as row n_res
+  auto emit_hyp = [&](uint32_t top) -> bool {
+    int body = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+      int32_t *dst = nullptr;
+      if (pass == 1) {
+        dst = alloc(body + n_extra);
+        if (!dst) return false;
+        dst = put_extras(dst, body);
+      }
+      int k = 0, last = 0;
+      bool prev_unk = false;
+      for (uint32_t h = hy[top].next; hy[h].next != kNone; h = hy[h].next) put_node(nodes[hy[h].node], dst, body, k, prev_unk, last);
+      body = k;
+    }
+    return true;
+  };
+  float fx_last = 0.f, fx_prev = 0.f, marginal = 0.f;          // mode 5: the perturbed scores of the last two results
+  uint32_t best_at = kNone;                                    // mode 5: the row of the search that is the best path
+  if (wor) {
+#pragma clang fp contract(off)
+    if (base) {
+      // the Viterbi path as a chain of hypotheses, EOS first, so that it is emitted like a result; its prev links
+      // stay as they are: a result is the best path when its nodes are (:782-786 compares the node vectors)
+      hy[0] = NbHyp{kNone, 1u, 0.f, 0.f};
+      n_hyp = 1;
+      for (uint32_t cur = nodes[1].prev;; cur = nodes[cur].prev) {
+        if (n_hyp >= a.max_hyps) { set_aside(); return; }
+        hy[n_hyp] = NbHyp{n_hyp - 1u, cur, 0.f, 0.f};
+        ++n_hyp;
+        if (cur == 0u) break;
+      }
+      if (!emit_hyp(n_hyp - 1u)) return;
+      res_score[0] = 0.f;                                      // "inclusion probability if we always include the best is 1"
+      a.res_count[s] = n_res = 1;
+    }
+    // ForwardAlgorithm (:200-216) in the reference's order and float arithmetic, as modes 3 and 4 run it: alpha of a node
+    // is that of its begin position, kept in the node's backtrace (Viterbi is done with it); nodes are sorted by position
+    int at = -1;
+    float acc = 0.f;
+    for (uint32_t i = 2; i <= n_nodes; ++i) {
+      const uint32_t nd = i < n_nodes ? i : 1u;                // EOS last
+      const int pos = nodes[nd].pos;
+      if (pos != at) {
+        at = pos;
+        for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
+          const NbNode &ln = nodes[end_idx[l]];
+          const float w = a.inv_theta * ln.score;
+          acc = lse(acc, w + ln.backtrace, l == end_off[pos]);
+        }
+      }
+      nodes[nd].backtrace = acc;
+    }
+    marginal = nodes[1].backtrace;
+    st = hashed_seed() + (static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull + 0x8EBC6AF09C88C6E3ull;
+  }
+  // Gumbel() (:61-70): -log(-log(u + 1e-7f)) in float, u uniform over the 2^24 floats k / 2^24.  Where u + 1e-7f rounds to
+  // 1 the reference returns +inf (two values of u); those are drawn again here.
+  auto gumbel = [&]() -> float {
+    for (;;) {
+      const float u = static_cast<float>(static_cast<uint32_t>(uniform() * 16777216.0)) * (1.f / 16777216.f);
+      const float t = u + 1e-7f;
+      if (t < 1.f) return -logf(-logf(t));
+    }
+  };
+  if (n_hyp >= a.max_hyps) { a.res_count[s] = 0; set_aside(); return; }
+  const uint32_t eos_hyp = n_hyp;
+  hy[n_hyp] = NbHyp{kNone, 1u, wor ? gumbel() : nodes[1].backtrace, 0.f};
+  ++n_hyp;
+  nb_heap_push(heap, &hn, hy, eos_hyp);
   while (hn > 0) {
     const uint32_t top = nb_heap_pop(heap, &hn, hy);
     const uint32_t node = hy[top].node;
     if (node == 0) {                                           // reached BOS: a complete path
-      // ids of the path, left to right (PopulateSentencePieceText :581-613)
-      int body = 0;
-      for (int pass = 0; pass < 2; ++pass) {
-        int32_t *dst = nullptr;
-        if (pass == 1) {
-          dst = alloc(body + n_extra);
-          if (!dst) return;
-          dst = put_extras(dst, body);
+      if (!emit_hyp(top)) return;
+      if (wor) {
+#pragma clang fp contract(off)
+        // its log probability (:799-809): the float sum of inv_theta * score, left to right, minus the marginal
+        float score = 0.f;
+        bool is_best = base != 0u;
+        uint32_t left = 0u;
+        for (uint32_t h = hy[top].next;; h = hy[h].next) {
+          const uint32_t nd = hy[h].node;
+          if (nodes[nd].prev != left) is_best = false;
+          if (hy[h].next == kNone) break;
+          const float w = a.inv_theta * nodes[nd].score;
+          score = score + w;
+          left = nd;
         }
-        int k = 0, last = 0;
-        bool prev_unk = false;
-        for (uint32_t h = hy[top].next; hy[h].next != 0xFFFFFFFFu; h = hy[h].next) put_node(nodes[hy[h].node], dst, body, k, prev_unk, last);
-        body = k;
+        if (is_best) best_at = n_res;
+        res_score[n_res] = score - marginal;
+        fx_prev = fx_last;
+        fx_last = hy[top].fx;
+      } else {
+        res_score[n_res] = hy[top].fx;
       }
-      res_score[n_res] = hy[top].fx;
       a.res_count[s] = ++n_res;
-      if (n_res == a.nbest) break;
+      if (n_res - base == want) break;
       continue;
     }
     const int pos = nodes[node].pos;
@@ -400,14 +584,37 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     if (hn + fan > kNbAgendaCap) { wv::atomic_or(a.status, kStNbestOverflow); return; }
     if (n_hyp + fan > a.max_hyps) { a.res_count[s] = 0; set_aside(); return; }      // again, with a larger hypothesis slice
     const float gx = hy[top].gx;
-    for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
-      const uint32_t ln = end_idx[l];
-      hy[n_hyp] = NbHyp{top, ln, nodes[ln].backtrace + gx, nodes[ln].score + gx};
-      nb_heap_push(heap, &hn, hy, n_hyp);
-      ++n_hyp;
+    if (wor) {
+#pragma clang fp contract(off)
+      // :428-450, float and double where the reference has them: everything here is float there (std::exp, std::log1p
+      // and std::abs of a float), adjusted_probs holds the float result widened
+      const float fx = hy[top].fx, Z = nodes[node].backtrace;
+      float max_score = -1e8f;
+      for (uint32_t l = end_off[pos], i = n_hyp; l < end_off[pos + 1]; ++l, ++i) {
+        const uint32_t ln = end_idx[l];
+        const float w = a.inv_theta * nodes[ln].score;
+        const float prob = gx + nodes[ln].backtrace + w - Z;
+        const float perturbed = prob + gumbel();
+        if (perturbed > max_score) max_score = perturbed;
+        hy[i] = NbHyp{top, ln, perturbed, prob};
+      }
+      for (uint32_t i = n_hyp; i < n_hyp + fan; ++i) {        // truncated Gumbel, arXiv 1903.06059 appendix B.3
+        const float perturbed = hy[i].fx;
+        const float v = fx - perturbed + log1pf(-expf(perturbed - max_score));
+        hy[i].fx = fx - fmaxf(0.f, v) - log1pf(expf(-fabsf(v)));
+        nb_heap_push(heap, &hn, hy, i);
+      }
+      n_hyp += fan;
+    } else {
+      for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
+        const uint32_t ln = end_idx[l];
+        hy[n_hyp] = NbHyp{top, ln, nodes[ln].backtrace + gx, nodes[ln].score + gx};
+        nb_heap_push(heap, &hn, hy, n_hyp);
+        ++n_hyp;
+      }
     }
     if (hn >= 10000u) {                                        // :487-514 keep the best min(512, 10 nbest)
-      const uint32_t keep = a.nbest * 10u < 512u ? a.nbest * 10u : 512u;
+      const uint32_t keep = want * 10u < 512u ? want * 10u : 512u;
       // pop the best `keep` into the (free) tail of the hypothesis slice, then rebuild the heap from them in that order
       if (n_hyp + keep > a.max_hyps) { a.res_count[s] = 0; set_aside(); return; }
       uint32_t *tmp = reinterpret_cast<uint32_t *>(hy + n_hyp);
@@ -416,6 +623,36 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
       for (uint32_t i = 0; i < keep; ++i) nb_heap_push(heap, &hn, hy, tmp[i]);
     }
   }
+  if (!wor) return;
+  // ---- :775-827.  kappa is the perturbed score of the last result once the best path is out of the samples (erased where
+  // it occurs, else the last sample goes); that last result is dropped, and every other score becomes the log of its
+  // inclusion probability.  A lattice with no more paths than samples therefore returns one result fewer than it has
+  // paths; where nothing is left the sentence owns no result (with include_best and ONE path the reference erases the
+  // best path and then reads the back of an empty vector: no result here either). ----
+  uint32_t m = n_res - base;
+  float kappa_f = fx_last;
+  if (base) {
+    if (best_at != kNone) {
+      if (best_at == n_res - 1u) kappa_f = fx_prev;
+      for (uint32_t k = best_at; k + 1u < n_res; ++k) { res_off[k] = res_off[k + 1]; res_len[k] = res_len[k + 1]; res_score[k] = res_score[k + 1]; }
+    } else {
+      kappa_f = fx_prev;
+    }
+    if (m > 0u) --m;
+  }
+  if (m == 0u) { a.res_count[s] = 0; return; }
+  --m;
+  const double kappa = static_cast<double>(kappa_f);
+  for (uint32_t k = base; k < base + m; ++k) {
+    if (res_score[k] != 0.f) {                                 // :814 "only modify non best sample inclusion probabilities"
+      const double x = static_cast<double>(res_score[k]) - kappa;
+      const double y = exp(x);
+      const double inc = x <= -10.0 ? x - (y / 2) + (y * y / 24) - ((y * y) * (y * y)) / 2880    // the log Gumbel survival function's series
+                                    : log(-expm1(-y));
+      res_score[k] = static_cast<float>(inc);
+    }
+  }
+  a.res_count[s] = base + m;
 }
 
 // Persistent body: lane l of wave w takes sentences w * 64 + l, + lanes of the launch, ...

@@ -1046,6 +1046,149 @@ class SentencePieceProcessor:
     nbest_encode = NBestEncode
     nbest_encode_as_immutable_proto = NBestEncodeAsImmutableProto
 
+    # ---------------------------------------------------- lattice scoring ----
+    def CalculateEntropyPacked(self, text, offsets, alpha):
+        """Packed host arrays -> ``float32[n]``: ``CalculateEntropy(input, alpha)`` of every sentence (unigram models
+        only).  The value is the reference's own float recurrence, not the exact entropy."""
+        self._need()
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        p = C.c_void_p()
+        self._check(self._lib.spmx_calculate_entropy_batch(self._h, text.ctypes.data if len(text) else None, offs.ctypes.data, n,
+                                                           C.c_float(alpha), C.byref(p)))
+        try:
+            return (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n,)).copy()
+                    if n else np.zeros(0, dtype=np.float32))
+        finally:
+            self._lib.spmx_free(p)
+
+    def CalculateEntropy(self, input, alpha, num_threads=None):
+        """``CalculateEntropy`` (python/src/sentencepiece/__init__.py:895-904): a float for a str, a list of floats
+        for a list.  ``num_threads`` is accepted and ignored: the batch is one device call."""
+        single, raw, text, offs = self._pack_items(input)
+        out = self.CalculateEntropyPacked(text, offs, alpha).tolist()
+        return out[0] if single else out
+
+    calculate_entropy = CalculateEntropy
+
+    def SampleEncodeAndScorePacked(self, text, offsets, num_samples=1, alpha=1.0, wor=False, include_best=False, seed=0,
+                                   spans=False, _keep_options=False):
+        """Packed host arrays -> ``(ids, id_offsets, scores, result_offsets)`` as ``NBestPacked`` gives them, with
+        ``(begin, end, nbegin, nend)`` appended under ``spans``: ``SampleEncodeAndScore`` of every sentence.  A
+        sentence for which the reference reports "SampleEncodeAndScore returns empty result." owns no result.  Draw j
+        of sentence i is keyed by ``(seed, i, j)``."""
+        self._need()
+        if not _keep_options:
+            self._apply(False, False, False)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        ps = [C.c_void_p() for _ in range(8 if spans else 4)]
+        fn = self._lib.spmx_sample_encode_and_score_batch_spans if spans else self._lib.spmx_sample_encode_and_score_batch
+        self._check(fn(self._h, text.ctypes.data if len(text) else None, offs.ctypes.data, n, int(num_samples), C.c_float(alpha),
+                       int(bool(wor)), int(bool(include_best)), int(seed), *[C.byref(p) for p in ps]))
+        try:
+            ro = np.ctypeslib.as_array(C.cast(ps[3], C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+            R = int(ro[n])
+            io = np.ctypeslib.as_array(C.cast(ps[1], C.POINTER(C.c_uint64)), shape=(R + 1,)).copy()
+            total = int(io[R])
+            ids = (np.ctypeslib.as_array(C.cast(ps[0], C.POINTER(C.c_int32)), shape=(total,)).copy()
+                   if total else np.zeros(0, dtype=np.int32))
+            sc = (np.ctypeslib.as_array(C.cast(ps[2], C.POINTER(C.c_float)), shape=(R,)).copy()
+                  if R else np.zeros(0, dtype=np.float32))
+            rest = tuple(self._spans_arrays(ps[4:], total)) if spans else ()
+        finally:
+            for p in ps:
+                self._lib.spmx_free(p)
+        return (ids, io, sc, ro) + rest
+
+    def SampleEncodeAndScore(self, input, out_type=None, add_bos=None, add_eos=None, reverse=None, emit_unk_piece=None,
+                             num_samples=None, alpha=None, wor=None, include_best=None, seed=None):
+        """``SampleEncodeAndScore`` (python/src/sentencepiece/__init__.py:679-753): per sentence a list of
+        ``(ids | pieces, score)``, or its ``NBestSentencePieceText`` under the proto out_types.  ``seed`` (not in the
+        reference, whose generator cannot be seeded): None draws a fresh one per call."""
+        from . import spt_proto
+        self._need()
+        out_type = self._out_type if out_type is None else out_type
+        a_bos = self._add_bos if add_bos is None else add_bos
+        a_eos = self._add_eos if add_eos is None else add_eos
+        rev = self._reverse if reverse is None else reverse
+        emit = self._emit_unk_piece if emit_unk_piece is None else emit_unk_piece
+        num_samples = 1 if num_samples is None else num_samples
+        alpha = 1.0 if alpha is None else alpha
+        wor = bool(wor)
+        include_best = bool(include_best)
+        if num_samples <= 0:
+            raise RuntimeError("num_examples must be positive")
+        if include_best and not wor:
+            raise RuntimeError('When include_best is True, We must specify "wor = True".')
+        proto = out_type in ("serialized_proto", "proto", "immutable_proto")
+        if not (proto or out_type is int or out_type is str or out_type == "str"):
+            raise RuntimeError("unknown output type")
+        if proto and any([a_bos, a_eos, rev, emit]):
+            raise NotImplementedError("add_bos, add_eos, reverse, and emit_unk_piece is not supported in proto API")
+        if seed is None:
+            if not hasattr(self, "_sample_calls"):
+                self._sample_calls = int.from_bytes(os.urandom(7), "little")
+            self._sample_calls += 1
+            seed = self._sample_calls
+        single, raw, text, offs = self._pack_items(input)
+        if not proto:
+            self._apply(a_bos, a_eos, rev)
+        try:
+            ids, io, sc, ro, b, e, nbg, nen = self.SampleEncodeAndScorePacked(text, offs, num_samples, alpha, wor, include_best, seed,
+                                                                              spans=True, _keep_options=not proto)
+            ro = ro.astype(np.int64)
+            if (ro[1:] == ro[:-1]).any():                         # sentencepiece_processor.cc:735, of that sentence
+                raise RuntimeError("SampleEncodeAndScore returns empty result.")
+            if out_type is int:
+                out = [[(ids[int(io[r]):int(io[r + 1])].tolist(), float(sc[r])) for r in range(ro[s], ro[s + 1])] for s in range(len(raw))]
+                return out[0] if single else out
+            norm, no, _ = self.NormalizePacked(text, offs)
+            sent = np.repeat(np.arange(len(raw)), ro[1:] - ro[:-1]).tolist()
+            rows = self._rows_from_spans(raw, norm.tobytes(), no, sent, ids, io, b, e, nbg, nen)
+        finally:
+            if not proto:
+                self._apply(False, False, False)
+        if not proto:
+            unk = self.IdToPiece(self.unk_id())
+            out = [[([(unk if emit and self.IsUnknown(t) else p.decode("utf-8", "surrogateescape")) for p, t, *_ in rows[r]], float(sc[r]))
+                    for r in range(ro[s], ro[s + 1])] for s in range(len(raw))]
+            return out[0] if single else out
+        out = []
+        for s in range(len(raw)):
+            per = [(float(sc[r]), rows[r]) for r in range(ro[s], ro[s + 1])]
+            if out_type == "immutable_proto":
+                views = []
+                for score, rw in per:
+                    v = spt_proto.ImmutableSentencePieceText(raw[s], [(p, t, sf if sf is not None else b"", pb, pe) for p, t, sf, pb, pe in rw],
+                                                             spt_proto.serialize(raw[s], rw, score))
+                    v.score = score
+                    views.append(v)
+                out.append(spt_proto.ImmutableNBestSentencePieceText(views))
+            else:
+                out.append(spt_proto.serialize_nbest([spt_proto.serialize(raw[s], rw, score) for score, rw in per]))
+        return out[0] if single else out
+
+    def SampleEncodeAndScoreAsPieces(self, input, num_samples=None, alpha=None, **kwargs):
+        return self.SampleEncodeAndScore(input=input, num_samples=num_samples, alpha=alpha, out_type=str, **kwargs)
+
+    def SampleEncodeAndScoreAsIds(self, input, num_samples=None, alpha=None, **kwargs):
+        return self.SampleEncodeAndScore(input=input, num_samples=num_samples, alpha=alpha, out_type=int, **kwargs)
+
+    def SampleEncodeAndScoreAsSerializedProto(self, input, num_samples=None, alpha=None, **kwargs):
+        return self.SampleEncodeAndScore(input=input, num_samples=num_samples, alpha=alpha, out_type="serialized_proto", **kwargs)
+
+    def SampleEncodeAndScoreAsImmutableProto(self, input, num_samples=None, alpha=None, **kwargs):
+        return self.SampleEncodeAndScore(input=input, num_samples=num_samples, alpha=alpha, out_type="immutable_proto", **kwargs)
+
+    sample_encode_and_score = SampleEncodeAndScore
+    sample_encode_and_score_as_pieces = SampleEncodeAndScoreAsPieces
+    sample_encode_and_score_as_ids = SampleEncodeAndScoreAsIds
+    sample_encode_and_score_as_serialized_proto = SampleEncodeAndScoreAsSerializedProto
+    sample_encode_and_score_as_immutable_proto = SampleEncodeAndScoreAsImmutableProto
+
     def Tokenize(self, input, **kwargs):
         """``Tokenize`` = ``Encode`` (:1009-1010)."""
         return self.Encode(input, **kwargs)
