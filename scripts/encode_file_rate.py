@@ -84,7 +84,7 @@ def main():
     lt, lo = text[:int(offs[n_list])], offs[:n_list + 1]
     blob = lt.tobytes()
     lo64 = lo.astype(np.int64)
-    items = [blob[lo64[i]:lo64[i + 1]].decode("utf-8") for i in range(n_list)]
+    items = [blob[lo64[i]:lo64[i + 1]] for i in range(n_list)]        # (bytes: the corpus has sentences that are not UTF-8)
     if hasattr(sp, "EncodePiecesPacked"):
         ts, r = timed(lambda: sp.EncodePiecesPacked(lt, lo), reps=3)
         out["pieces_packed"] = rate(ts, n_list)

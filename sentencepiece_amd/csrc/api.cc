@@ -99,6 +99,14 @@ struct DevBuf {
   }
   void Free() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+// a DevBuf that one call (or one of its workers) owns: freed with its scope
+template <typename T>
+struct ScratchBuf : DevBuf<T> {
+  ScratchBuf() = default;
+  ScratchBuf(const ScratchBuf &) = delete;
+  ScratchBuf &operator=(const ScratchBuf &) = delete;
+  ~ScratchBuf() { this->Free(); }
+};
 
 // Pinned host memory NEAR THE GPU: hipHostMalloc places its pages by the calling thread's memory policy, and on a
 // two-socket host a staging buffer on the other socket makes every H2D / D2H copy cross the inter-socket link.  While one
@@ -267,6 +275,7 @@ struct Workspace {
     d_norm.Free(); d_nbest_scratch.Free(); d_slab.Free(); d_pool.Free(); d_sent_status.Free(); d_flags.Free(); d_res_off.Free();
     d_res_score.Free(); d_dyn_tag.Free(); d_dyn_ent.Free(); d_dyn_list.Free(); d_resume.Free(); d_text.Free(); d_offs.Free(); d_id_offs.Free(); d_ids.Free(); d_dn_text.Free(); d_dn_offs.Free();
     d_tt_len.Free(); d_tt_rec.Free(); d_tt_start.Free(); d_tt_noffs.Free(); d_tt_out.Free();
+    d_lit_bytes.Free(); d_lit_offs.Free(); d_dec_ids.Free(); d_dec_poffs.Free();
     h_text.Free(); h_offs.Free(); h_id_offs.Free();
     if (d_ctrl) (void)hipFree(d_ctrl);
     if (h_ctrl) (void)hipHostFree(h_ctrl);
@@ -432,6 +441,19 @@ struct Lease {
     h->pool.push_back(std::move(ws));
   }
 };
+
+// The grow-and-retry protocol of the calls that report their need: call() runs with `buf` reserved for a guess and
+// writes the elements it produced, or would have, to *need; buf holds `slack` elements more than that.  Only a
+// kResourceExhausted that needs more than buf.cap is tried again, once, at exactly the need.
+template <typename T, typename CallFn>
+int GrowOnce(spmx_handle *h, DevBuf<T> &buf, uint64_t want, const uint64_t *need, uint64_t slack, CallFn call) {
+  for (bool again = false;; again = true) {
+    HIP_OR_RETURN(h, buf.Reserve(want));
+    const int rc = call();
+    if (again || rc != kResourceExhausted || *need + slack <= buf.cap) return rc;
+    want = *need + slack;
+  }
+}
 
 thread_local uint64_t t_upload_bytes = 0;   // device bytes the tables of the handle being loaded take (spmx_handle_info)
 template <typename T>
@@ -1735,14 +1757,11 @@ int DecodeDevice(spmx_handle *h, Workspace *ws, const int32_t *d_ids, const uint
   if (total_bytes) *total_bytes = 0;
   if (!d_id_offsets || !d_text_offsets) return Fail(h, kInvalidArgument, "null offsets");
   HIP_OR_RETURN(h, ws->d_dn_offs.Reserve(n + 1));
-  uint64_t cap = ws->d_dn_text.cap ? ws->d_dn_text.cap : (1u << 20), total = 0;
-  int rc = kOk;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    HIP_OR_RETURN(h, ws->d_dn_text.Reserve(cap));
-    rc = DecodeRaw(h, ws, d_ids, d_id_offsets, n, ws->d_dn_text.p, ws->d_dn_text.cap, ws->d_dn_offs.p, stream, &total, so);
-    if (rc != kResourceExhausted || total <= ws->d_dn_text.cap) break;
-    cap = total + 64;
-  }
+  uint64_t total = 0;
+  DevBuf<uint8_t> &raw = ws->d_dn_text;
+  int rc = GrowOnce(h, raw, raw.cap ? raw.cap : (1u << 20), &total, 64, [&] {
+    return DecodeRaw(h, ws, d_ids, d_id_offsets, n, raw.p, raw.cap, ws->d_dn_offs.p, stream, &total, so);
+  });
   if (raw_bytes) *raw_bytes = total;
   if (rc != kOk) return rc;
   rc = NormalizeDevice(h, ws, ws->d_dn_text.p, ws->d_dn_offs.p, n, d_text, d_text ? text_capacity : 0, d_text_offsets, nullptr, stream,
@@ -1780,6 +1799,103 @@ int Guard(spmx_handle *h, F f) {
   } catch (...) {
     return Fail(h, kInternal, "unknown exception");
   }
+}
+
+/* ---- the chunk pipeline of the file calls (spmx_encode_file, spmx_count_file, spmx_decode_file) -------------------------
+ * The input is mapped and cut into chunks of about 64 MiB that end after a line end (SPMX_FILE_CHUNK: 4096 at least).
+ * RunChunks: T = min(host_threads, 4, n_chunks) workers, each with a leased workspace and a Scratch of the call's (freed
+ * before the workspace goes back), take the chunks w, w + T, ...  process(s, k) brings chunk k up to its finished host
+ * image with no lock held; commit(s, k) runs under the mutex, `ordered` in chunk order (the writer).  Failure: the lowest
+ * failing chunk's status and text; no chunk above a known failure is started or committed, those below it still are. */
+struct MappedFile {
+  const uint8_t *p = nullptr;
+  uint64_t size = 0;
+  int Open(spmx_handle *h, const std::string &path) {
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return Fail(h, kNotFound, "\"" + path + "\": No such file or directory");
+    struct stat sb;
+    void *m = nullptr;
+    const bool ok = fstat(fd, &sb) == 0 && (sb.st_size == 0 || (m = mmap(nullptr, sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0)) != MAP_FAILED);
+    close(fd);
+    if (!ok) return Fail(h, kInternal, "cannot map \"" + path + "\"");
+    p = static_cast<const uint8_t *>(m);
+    size = static_cast<uint64_t>(sb.st_size);
+    return kOk;
+  }
+  ~MappedFile() { if (p) munmap(const_cast<uint8_t *>(p), size); }
+};
+
+struct OutFile {
+  FILE *f = nullptr;
+  bool Open(const std::string &path) { return (f = fopen(path.c_str(), "wb")) != nullptr; }
+  ~OutFile() { if (f) fclose(f); }
+};
+
+uint64_t FileChunkTarget() {
+  const char *e = getenv("SPMX_FILE_CHUNK");
+  return e ? std::max<uint64_t>(4096, strtoull(e, nullptr, 10)) : 64ull << 20;
+}
+
+// chunk k: the bytes [cut[k], cut[k + 1]), ending after the first line end at or behind `target` bytes
+std::vector<uint64_t> CutAtLineEnds(const uint8_t *p, uint64_t size, uint64_t target) {
+  std::vector<uint64_t> cut(1, 0);
+  while (cut.back() < size) {
+    uint64_t e = cut.back() + target;
+    if (e >= size) e = size;
+    else {
+      const void *nl = memchr(p + e, '\n', size - e);
+      e = nl ? static_cast<uint64_t>(static_cast<const uint8_t *>(nl) - p) + 1 : size;
+    }
+    cut.push_back(e);
+  }
+  return cut;
+}
+
+template <typename Scratch, typename ProcessFn, typename CommitFn>
+int RunChunks(spmx_handle *h, uint64_t n_chunks, bool ordered, ProcessFn process, CommitFn commit) {
+  int T = h->host_threads < 4 ? h->host_threads : 4;
+  if (static_cast<uint64_t>(T) > n_chunks) T = static_cast<int>(n_chunks ? n_chunks : 1);
+  std::mutex mu;
+  std::condition_variable cv;
+  uint64_t next_commit = 0;
+  uint64_t fail_chunk = ~0ull;          // the lowest failing chunk so far, its status and text
+  int fail_rc = kOk;
+  std::string fail_err;
+  auto worker = [&](int w) {
+    uint64_t k = static_cast<uint64_t>(w);
+    auto body = [&]() -> int {
+      HIP_OR_RETURN(h, hipSetDevice(h->device));
+      Lease L(h);
+      if (int r = L.Ready(); r != kOk) return r;
+      Scratch s;
+      s.ws = L.ws.get();
+      for (; k < n_chunks; k += static_cast<uint64_t>(T)) {
+        { std::lock_guard<std::mutex> l(mu); if (fail_chunk < k) return kOk; }
+        if (int r = process(s, k); r != kOk) return r;
+        std::unique_lock<std::mutex> l(mu);
+        if (ordered) cv.wait(l, [&] { return next_commit == k || fail_chunk < k; });
+        if (fail_chunk < k) return kOk;
+        const int r = commit(s, k);
+        next_commit = k + 1;
+        cv.notify_all();
+        if (r != kOk) return r;
+      }
+      return kOk;
+    };
+    int rc = kOk;
+    try { rc = body(); } catch (const std::bad_alloc &) { rc = kResourceExhausted; t_error = "out of host memory"; } catch (...) { rc = kInternal; t_error = "unknown exception"; }
+    if (rc != kOk) {
+      const std::string err = t_error;
+      std::lock_guard<std::mutex> l(mu);
+      if (k < fail_chunk) { fail_chunk = k; fail_rc = rc; fail_err = err; }
+      cv.notify_all();
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int w = 1; w < T; ++w) pool.emplace_back(worker, w);
+  worker(0);
+  for (auto &t : pool) t.join();
+  return fail_rc == kOk ? kOk : Fail(h, fail_rc, fail_err);
 }
 
 }  // namespace
@@ -2189,23 +2305,20 @@ int EncodeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, u
   // offsets are used as given: the kernels address text + offs[i], so rebase the text pointer instead (they read
   // aligned 16-byte blocks of the absolute address: nothing before the staging buffer, at most 15 bytes of its slack after)
   const uint8_t *d_text = ws->d_text.p - base;
-  uint64_t cap = IdsGuess(h, text_bytes, n), total = 0, failed = 0;
-  int rc = kOk;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    e = ws->d_ids.Reserve(cap);
-    if (e == hipSuccess && spans) e = ws->d_span_begin.Reserve(ws->d_ids.cap);
+  uint64_t total = 0, failed = 0;
+  const int rc = GrowOnce(h, ws->d_ids, IdsGuess(h, text_bytes, n), &total, 0, [&]() -> int {
+    e = hipSuccess;
+    if (spans) e = ws->d_span_begin.Reserve(ws->d_ids.cap);
     if (e == hipSuccess && spans) e = ws->d_span_end.Reserve(ws->d_ids.cap);
     if (e == hipSuccess && nspans) e = ws->d_nspan_begin.Reserve(ws->d_ids.cap);
     if (e == hipSuccess && nspans) e = ws->d_nspan_end.Reserve(ws->d_ids.cap);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(ids)");
-    rc = EncodeDevice(h, ws, d_text, text_bytes, ws->d_offs.p, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
-                      status ? ws->d_sent_status.p : nullptr, st, &total, &failed,
-                      spans ? ws->d_span_begin.p : nullptr, spans ? ws->d_span_end.p : nullptr,
-                      nspans ? ws->d_nspan_begin.p : nullptr, nspans ? ws->d_nspan_end.p : nullptr);
-    if (rc != kResourceExhausted || total <= ws->d_ids.cap) break;
-    cap = total;
-  }
-  if (rc != kOk) { drop(); return rc; }
+    if (e != hipSuccess) return FailHip(h, e, "hipMalloc(spans)");
+    return EncodeDevice(h, ws, d_text, text_bytes, ws->d_offs.p, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
+                        status ? ws->d_sent_status.p : nullptr, st, &total, &failed,
+                        spans ? ws->d_span_begin.p : nullptr, spans ? ws->d_span_end.p : nullptr,
+                        nspans ? ws->d_nspan_begin.p : nullptr, nspans ? ws->d_nspan_end.p : nullptr);
+  });
+  if (rc != kOk) { drop(); return rc; }      // (a failed reservation included)
   const size_t tn = total ? total : 1;
   int32_t *hi = static_cast<int32_t *>(outs[1] = malloc(tn * sizeof(int32_t)));
   uint8_t *hs = status ? static_cast<uint8_t *>(outs[2] = malloc(n)) : nullptr;
@@ -2400,15 +2513,11 @@ int EncodeBatchPipelined(spmx_handle *const *hs, int n_h, const char *text, cons
         }
         if (bytes) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_text.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
         HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, ws->h_offs.p, (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        uint64_t want = IdsGuess(h, bytes, cnt), total = 0, failed = 0;
-        int r = kOk;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-          HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
-          r = EncodeDevice(h, ws, ws->d_text.p, bytes, ws->d_offs.p, cnt, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
-                           ws->d_sent_status.p, st, &total, &failed);
-          if (r != kResourceExhausted || total <= ws->d_ids.cap) break;
-          want = total;
-        }
+        uint64_t total = 0, failed = 0;
+        const int r = GrowOnce(h, ws->d_ids, IdsGuess(h, bytes, cnt), &total, 0, [&] {
+          return EncodeDevice(h, ws, ws->d_text.p, bytes, ws->d_offs.p, cnt, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
+                              ws->d_sent_status.p, st, &total, &failed);
+        });
         if (r != kOk) return r;
         uint64_t my_base = 0;
         {                                                        // the chunk's place in the CSR
@@ -2620,14 +2729,10 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
     if (text_bytes) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_text.p, text + base, text_bytes, hipMemcpyHostToDevice, st));
     HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     const uint8_t *d_text = ws->d_text.p - base;
-    uint64_t ncap = 2 * text_bytes + 4 * n + 64, ntotal = 0;
-    int rc = kOk;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      HIP_OR_RETURN(h, ws->d_norm.Reserve(ncap));
-      rc = NormalizeDevice(h, ws, d_text, ws->d_offs.p, n, ws->d_norm.p, ws->d_norm.cap, ws->d_id_offs.p, nullptr, st, &ntotal, true);
-      if (rc != kResourceExhausted || ntotal <= ws->d_norm.cap) break;
-      ncap = ntotal;
-    }
+    uint64_t ntotal = 0;
+    int rc = GrowOnce(h, ws->d_norm, 2 * text_bytes + 4 * n + 64, &ntotal, 0, [&] {
+      return NormalizeDevice(h, ws, d_text, ws->d_offs.p, n, ws->d_norm.p, ws->d_norm.cap, ws->d_id_offs.p, nullptr, st, &ntotal, true);
+    });
     if (rc != kOk) return rc;
     const uint32_t K = static_cast<uint32_t>(nbest_size);
     if (n * K + 1 > (1ull << 32)) return Fail(h, kInvalidArgument, "too many results for one batch");
@@ -3111,18 +3216,13 @@ int spmx_normalize_batch(spmx_handle *h, const char *text, const uint64_t *offse
     if (e == hipSuccess) e = hipMemcpyAsync(ws->d_offs.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) { free(ho); return FailHip(h, e, "staging the batch"); }
     const uint8_t *d_text = ws->d_text.p - base;
-    uint64_t cap = 2 * text_bytes + 4 * n + 64, total = 0;
-    int rc = kOk;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      e = ws->d_norm.Reserve(cap);
-      if (e == hipSuccess && norm_to_orig) e = ws->d_span_begin.Reserve(cap + n + 1);
-      if (e != hipSuccess) { free(ho); return FailHip(h, e, "hipMalloc(norm)"); }
-      rc = NormalizeDevice(h, ws, d_text, ws->d_offs.p, n, ws->d_norm.p, ws->d_norm.cap, ws->d_id_offs.p,
-                           norm_to_orig ? ws->d_span_begin.p : nullptr, st, &total);
-      if (rc != kResourceExhausted || total <= ws->d_norm.cap) break;
-      cap = total;
-    }
-    if (rc != kOk) { free(ho); return rc; }
+    uint64_t total = 0;
+    const int rc = GrowOnce(h, ws->d_norm, 2 * text_bytes + 4 * n + 64, &total, 0, [&]() -> int {
+      if (norm_to_orig) HIP_OR_RETURN(h, ws->d_span_begin.Reserve(ws->d_norm.cap + n + 1));
+      return NormalizeDevice(h, ws, d_text, ws->d_offs.p, n, ws->d_norm.p, ws->d_norm.cap, ws->d_id_offs.p,
+                             norm_to_orig ? ws->d_span_begin.p : nullptr, st, &total);
+    });
+    if (rc != kOk) { free(ho); return rc; }      // (a failed reservation included)
     char *ht = static_cast<char *>(malloc(total ? total : 1));
     uint32_t *hn = norm_to_orig ? static_cast<uint32_t *>(malloc((total + n + 1) * sizeof(uint32_t))) : nullptr;
     if (!ht || (norm_to_orig && !hn)) { free(ho); free(ht); free(hn); return Fail(h, kResourceExhausted, "out of host memory"); }
@@ -3304,7 +3404,7 @@ int DecodeBatchHost(spmx_handle *h, const int32_t *ids, const uint64_t *id_offse
     }
     if (e != hipSuccess) { free(ho); return FailHip(h, e, "staging the ids"); }
     const int32_t *d_ids = ws->d_ids.p - base;     // the kernels address ids + id_offsets[i]
-    uint64_t cap = n_ids * 6 + 64, total = 0, raw = 0;
+    uint64_t total = 0, raw = 0;
     int rc = kOk;
     DecodeSpanOut so{};
     if (sp) {      // at most kMaxExtra pieces of the extra options on either side of a sentence
@@ -3316,13 +3416,10 @@ int DecodeBatchHost(spmx_handle *h, const int32_t *ids, const uint64_t *id_offse
       if (e3 != hipSuccess) { free(ho); return FailHip(h, e3, "hipMalloc(spans)"); }
       so.ids = ws->d_dec_ids.p; so.begin = ws->d_span_begin.p; so.end = ws->d_span_end.p; so.offs = ws->d_dec_poffs.p;
     }
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      if (hipError_t e2 = ws->d_text.Reserve(cap); e2 != hipSuccess) { free(ho); return FailHip(h, e2, "hipMalloc(text)"); }
-      rc = DecodeDevice(h, ws, d_ids, ws->d_offs.p, n, ws->d_text.p, ws->d_text.cap, ws->d_id_offs.p, st, &total, sp ? &so : nullptr, &raw);
-      if (rc != kResourceExhausted || total <= ws->d_text.cap) break;
-      cap = total;
-    }
-    if (rc != kOk) { free(ho); return rc; }
+    rc = GrowOnce(h, ws->d_text, n_ids * 6 + 64, &total, 0, [&] {
+      return DecodeDevice(h, ws, d_ids, ws->d_offs.p, n, ws->d_text.p, ws->d_text.cap, ws->d_id_offs.p, st, &total, sp ? &so : nullptr, &raw);
+    });
+    if (rc != kOk) { free(ho); return rc; }      // (a failed reservation included)
     if (sp) {
       const uint64_t np = so.total;
       int32_t *hi = static_cast<int32_t *>(malloc((np ? np : 1) * sizeof(int32_t)));
@@ -3520,17 +3617,24 @@ int EncodeForPieces(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64
       rc != kOk)
     return rc;
   HIP_OR_RETURN(h, ws->d_tt_noffs.Reserve(n + 1));
-  uint64_t ncap = 2 * text_bytes + 4 * n + 64, ntotal = 0;
-  int rc = kOk;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    HIP_OR_RETURN(h, ws->d_norm.Reserve(ncap + 16));
-    rc = NormalizeDevice(h, ws, d_text, d_offsets, n, ws->d_norm.p, ws->d_norm.cap - 16, ws->d_tt_noffs.p, nullptr, stream, &ntotal);
-    if (rc != kResourceExhausted || ntotal + 16 <= ws->d_norm.cap) break;
-    ncap = ntotal;
-  }
+  uint64_t ntotal = 0;                     // (the 16 bytes of slack are not the normalizer's to fill)
+  const int rc = GrowOnce(h, ws->d_norm, 2 * text_bytes + 4 * n + 64 + 16, &ntotal, 16, [&] {
+    return NormalizeDevice(h, ws, d_text, d_offsets, n, ws->d_norm.p, ws->d_norm.cap - 16, ws->d_tt_noffs.p, nullptr, stream, &ntotal);
+  });
   if (rc != kOk) return rc;
   *src = PieceSource{ws->d_nspan_begin.p, ws->d_nspan_end.p, ws->d_norm.p, ws->d_tt_noffs.p};
   return kOk;
+}
+
+// Encode into the workspace's id arena (d_ids, grown once to the reported need) and d_id_offs, which the caller has
+// reserved.  src null: the ids alone; else the spans form and the normalized text as well, for the piece writer.
+int EncodeIntoArena(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                    hipStream_t stream, uint64_t *total, PieceSource *src) {
+  return GrowOnce(h, ws->d_ids, IdsGuess(h, text_bytes, n), total, 0, [&] {
+    return src ? EncodeForPieces(h, ws, d_text, text_bytes, d_offsets, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p, stream, total, src)
+               : EncodeDevice(h, ws, d_text, text_bytes, d_offsets, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p, nullptr, stream, total,
+                              nullptr);
+  });
 }
 
 // text -> piece lines with the ids in the workspace (d_ids, d_id_offs); d_out null: the image goes to ws->d_tt_out
@@ -3540,16 +3644,9 @@ int PieceLines(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t te
   *out_bytes = 0;
   if (n == 0) return kOk;
   HIP_OR_RETURN(h, ws->d_id_offs.Reserve(n + 1));
-  uint64_t want = IdsGuess(h, text_bytes, n), total = 0;
+  uint64_t total = 0;
   PieceSource src{};
-  int rc = kOk;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
-    rc = EncodeForPieces(h, ws, d_text, text_bytes, d_offsets, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p, stream, &total, &src);
-    if (rc != kResourceExhausted || total <= ws->d_ids.cap) break;
-    want = total;
-  }
-  if (rc != kOk) return rc;
+  if (int rc = EncodeIntoArena(h, ws, d_text, text_bytes, d_offsets, n, stream, &total, &src); rc != kOk) return rc;
   *n_ids = total;
   return TokenText(h, ws, 1, true, ws->d_ids.p, ws->d_id_offs.p, n, total, &src, nullptr, d_out, out_capacity,
                    grow ? &ws->d_tt_out : nullptr, stream, out_bytes);
@@ -3640,15 +3737,8 @@ int spmx_encode_batch_pieces(spmx_handle *h, const char *text, const uint64_t *o
       if (text_bytes) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_text.p, text + base, text_bytes, hipMemcpyHostToDevice, st));
       HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
       const uint8_t *d_text = ws->d_text.p - base;        // (the kernels address text + offs[i]: EncodeBatchHost)
-      uint64_t want = IdsGuess(h, text_bytes, n);
       PieceSource src{};
-      int rc = kOk;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
-        rc = EncodeForPieces(h, ws, d_text, text_bytes, ws->d_offs.p, n, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p, st, &total, &src);
-        if (rc != kResourceExhausted || total <= ws->d_ids.cap) break;
-        want = total;
-      }
+      int rc = EncodeIntoArena(h, ws, d_text, text_bytes, ws->d_offs.p, n, st, &total, &src);
       if (rc != kOk) return rc;
       rc = TokenText(h, ws, 1, false, ws->d_ids.p, ws->d_id_offs.p, n, total, &src, nullptr, nullptr, 0, &ws->d_tt_out, st, &pbytes);
       if (rc != kOk) return rc;
@@ -3673,14 +3763,65 @@ int spmx_encode_batch_pieces(spmx_handle *h, const char *text, const uint64_t *o
   });
 }
 
+namespace {
+// A text worker's scratch (chunk pipeline) and its front end: chunk -> pinned staging copy -> H2D -> spmx_split_lines
+// (getline semantics, on the device) -> encode into the workspace's id arena; `piece`: on to the piece lines, whose image
+// lands in ws->d_tt_out.
+struct TextChunk {
+  Workspace *ws = nullptr;
+  ScratchBuf<uint8_t> d_file;
+  uint64_t n_lines = 0, total = 0, image = 0;
+};
+int EncodeChunk(spmx_handle *h, TextChunk &c, const uint8_t *src, uint64_t bytes, bool piece) {
+  Workspace *ws = c.ws;
+  hipStream_t st = ws->stream;
+  uint64_t nl = 0;
+  for (const uint8_t *p = src, *e = src + bytes; p < e;) {
+    const void *q = memchr(p, '\n', static_cast<size_t>(e - p));
+    if (!q) break;
+    ++nl;
+    p = static_cast<const uint8_t *>(q) + 1;
+  }
+  const uint64_t lines = nl + (bytes && src[bytes - 1] != '\n' ? 1 : 0);
+  HIP_OR_RETURN(h, ws->h_text.Reserve(bytes + 32));
+  HIP_OR_RETURN(h, c.d_file.Reserve(bytes + 32));
+  HIP_OR_RETURN(h, ws->d_text.Reserve(bytes + 32));
+  HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 2));
+  HIP_OR_RETURN(h, ws->d_id_offs.Reserve(lines + 2));
+  memcpy(ws->h_text.p, src, bytes);
+  HIP_OR_RETURN(h, hipMemcpyAsync(c.d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
+  uint64_t text_bytes = 0;
+  c.n_lines = c.total = c.image = 0;
+  int r = spmx_split_lines_device(h, c.d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &c.n_lines, &text_bytes);
+  if (r != kOk) return r;
+  if (piece) return PieceLines(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, c.n_lines, nullptr, 0, true, st, &c.total, &c.image);
+  return EncodeIntoArena(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, c.n_lines, st, &c.total, nullptr);
+}
+
+// absl::StrJoin(ids, " ") + '\n' per line (spm_encode_main.cc:116-119) into w, which holds 11 bytes per id and one per
+// line; returns the image's end.  Plain pointers, so that no byte written makes the loop load one of them again.
+char *FormatIdLines(const int32_t *ids, const uint64_t *io, uint64_t n_lines, char *w) {
+  char tmp[16];
+  for (uint64_t s = 0; s < n_lines; ++s) {
+    const uint64_t b = io[s], e = io[s + 1];
+    for (uint64_t x = b; x < e; ++x) {
+      if (x > b) *w++ = ' ';
+      int v = ids[x], len = 0;
+      do { tmp[len++] = static_cast<char>('0' + v % 10); v /= 10; } while (v);
+      while (len) *w++ = tmp[--len];
+    }
+    *w++ = '\n';
+  }
+  return w;
+}
+}  // namespace
+
 /* ---- corpus file -> ids (the caller-side loop of spm_encode, src/spm_encode_main.cc:159-165) -------------------------
- * mmap the input, cut it into chunks that end at a line end, and run them through a pipeline of worker threads (each
- * with a workspace and a stream): pinned staging copy -> H2D -> spmx_split_lines (getline semantics, on the device)
- * -> encode -> format -> D2H.  A writer keeps the chunks in order.  format "id": one line of space-separated ids per
- * input line, as `spm_encode --output_format=id` writes; "piece": the pieces joined with ' ', spm_encode's default; both
- * images are written on the device (kernels_tokentext.h) and come back in one D2H.  "bin": out_path gets the ids (int32,
- * flat), out_path + ".idx" the n + 1 uint64 offsets.  SPMX_FILE_CHUNK sets the chunk size (spmx_decode_file);
- * SPMX_ID_HOST_FORMAT=1 keeps the ids of format "id" on the host's formatting loop (A/B). */
+ * The chunk pipeline with, per chunk, EncodeChunk -> format -> D2H, and a writer that keeps the chunks in order.  format
+ * "id": one line of space-separated ids per input line, as `spm_encode --output_format=id` writes; "piece": the pieces
+ * joined with ' ', spm_encode's default; both images are written on the device (kernels_tokentext.h) and come back in one
+ * D2H.  "bin": out_path gets the ids (int32, flat), out_path + ".idx" the n + 1 uint64 offsets.  SPMX_ID_HOST_FORMAT=1
+ * keeps the ids of format "id" on the host's formatting loop (A/B). */
 int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *format, uint64_t *n_sentences,
                      uint64_t *n_ids) {
   if (!h) return kInvalidArgument;
@@ -3690,167 +3831,63 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
     const std::string fmt = format ? format : "id";
     const bool bin = fmt == "bin", piece = fmt == "piece";
     if (!bin && !piece && fmt != "id") return Fail(h, kInvalidArgument, "format must be \"id\", \"piece\" or \"bin\"");
-    const bool host_format = getenv("SPMX_ID_HOST_FORMAT") != nullptr;
-    const int fd = open(in_path ? in_path : "", O_RDONLY);
-    if (fd < 0) return Fail(h, kNotFound, std::string("\"") + (in_path ? in_path : "") + "\": No such file or directory");
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) { close(fd); return Fail(h, kInternal, "fstat failed"); }
-    const uint64_t size = static_cast<uint64_t>(sb.st_size);
-    const uint8_t *file = nullptr;
-    if (size) {
-      void *m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m == MAP_FAILED) { close(fd); return Fail(h, kInternal, "mmap failed"); }
-      file = static_cast<const uint8_t *>(m);
-    }
-    close(fd);
-    FILE *out = fopen(out_path ? out_path : "", "wb");
-    FILE *idx = nullptr;
-    if (out && bin) idx = fopen((std::string(out_path) + ".idx").c_str(), "wb");
-    if (!out || (bin && !idx)) {
-      if (out) fclose(out);
-      if (file) munmap(const_cast<uint8_t *>(file), size);
-      return Fail(h, kPermissionDenied, std::string("cannot write \"") + (out_path ? out_path : "") + "\"");
-    }
-    // chunks of about 64 MiB that end after a line end
-    std::vector<uint64_t> cut(1, 0);
-    uint64_t target = 64ull << 20;
-    if (const char *e = getenv("SPMX_FILE_CHUNK")) {
-      const unsigned long long v = strtoull(e, nullptr, 10);
-      target = v < 4096 ? 4096 : v;
-    }
-    while (cut.back() < size) {
-      uint64_t e = cut.back() + target;
-      if (e >= size) e = size;
-      else {
-        const void *nl = memchr(file + e, '\n', size - e);
-        e = nl ? static_cast<uint64_t>(static_cast<const uint8_t *>(nl) - file) + 1 : size;
-      }
-      cut.push_back(e);
-    }
-    const uint64_t n_chunks = cut.size() - 1;
-    int T = h->host_threads < 4 ? h->host_threads : 4;
-    if (static_cast<uint64_t>(T) > n_chunks) T = static_cast<int>(n_chunks ? n_chunks : 1);
-    std::mutex mu;
-    std::condition_variable cv;
-    uint64_t next_write = 0, sent_total = 0, id_total = 0;
-    int first_rc = kOk;
-    std::string first_err;
-    auto worker = [&](int w) {
-      auto body = [&]() -> int {
-        HIP_OR_RETURN(h, hipSetDevice(h->device));
-        Lease L(h);
-        if (int r = L.Ready(); r != kOk) return r;
-        Workspace *ws = L.ws.get();
-        hipStream_t st = ws->stream;
-        DevBuf<uint8_t> d_file;
-        struct Guard2 { DevBuf<uint8_t> &b; ~Guard2() { b.Free(); } } g2{d_file};
-        std::vector<int32_t> ids;
-        std::vector<uint64_t> io;
-        std::string formatted;
-        for (uint64_t k = static_cast<uint64_t>(w); k < n_chunks; k += static_cast<uint64_t>(T)) {
-          const uint64_t bytes = cut[k + 1] - cut[k];
-          const uint8_t *src = file + cut[k];
-          uint64_t nl = 0;
-          for (const uint8_t *p = src, *e = src + bytes; p < e;) {
-            const void *q = memchr(p, '\n', static_cast<size_t>(e - p));
-            if (!q) break;
-            ++nl;
-            p = static_cast<const uint8_t *>(q) + 1;
-          }
-          const uint64_t lines = nl + (bytes && src[bytes - 1] != '\n' ? 1 : 0);
-          HIP_OR_RETURN(h, ws->h_text.Reserve(bytes + 32));
-          HIP_OR_RETURN(h, d_file.Reserve(bytes + 32));
-          HIP_OR_RETURN(h, ws->d_text.Reserve(bytes + 32));
-          HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 2));
-          HIP_OR_RETURN(h, ws->d_id_offs.Reserve(lines + 2));
-          memcpy(ws->h_text.p, src, bytes);
-          HIP_OR_RETURN(h, hipMemcpyAsync(d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
-          uint64_t n_lines = 0, text_bytes = 0;
-          int r = spmx_split_lines_device(h, d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &n_lines, &text_bytes);
-          if (r != kOk) return r;
-          uint64_t want = IdsGuess(h, text_bytes, n_lines), total = 0, image = 0;
-          if (piece) {
-            r = PieceLines(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, nullptr, 0, true, st, &total, &image);
-            if (r != kOk) return r;
-          } else {
-            for (int attempt = 0; attempt < 2; ++attempt) {
-              HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
-              r = EncodeDevice(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
-                               nullptr, st, &total, nullptr);
-              if (r != kResourceExhausted || total <= ws->d_ids.cap) break;
-              want = total;
-            }
-            if (r != kOk) return r;
-          }
-          const bool device_image = piece || (!bin && !host_format);
-          if (device_image) {                          // the finished image in one D2H
-            if (!piece) {
-              r = TokenText(h, ws, 0, true, ws->d_ids.p, ws->d_id_offs.p, n_lines, total, nullptr, nullptr, nullptr, 0, &ws->d_tt_out, st, &image);
-              if (r != kOk) return r;
-            }
-            HIP_OR_RETURN(h, ws->h_text.Reserve(image + 32));
-            if (image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, ws->d_tt_out.p, image, hipMemcpyDeviceToHost, st));
-            HIP_OR_RETURN(h, hipStreamSynchronize(st));
-          } else {
-            ids.resize(total);
-            io.resize(n_lines + 1);
-            if (total) HIP_OR_RETURN(h, hipMemcpyAsync(ids.data(), ws->d_ids.p, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIP_OR_RETURN(h, hipMemcpyAsync(io.data(), ws->d_id_offs.p, (n_lines + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-            HIP_OR_RETURN(h, hipStreamSynchronize(st));
-          }
-          if (!bin && !device_image) {                            // absl::StrJoin(ids, " ") per line (spm_encode_main.cc:116-119)
-            formatted.clear();
-            formatted.reserve(total * 6 + n_lines);
-            char tmp[16];
-            for (uint64_t s2 = 0; s2 < n_lines; ++s2) {
-              for (uint64_t x = io[s2]; x < io[s2 + 1]; ++x) {
-                if (x > io[s2]) formatted.push_back(' ');
-                int v = ids[x], len = 0;
-                do { tmp[len++] = static_cast<char>('0' + v % 10); v /= 10; } while (v);
-                while (len) formatted.push_back(tmp[--len]);
-              }
-              formatted.push_back('\n');
-            }
-          }
-          std::unique_lock<std::mutex> l(mu);
-          cv.wait(l, [&] { return next_write == k || first_rc != kOk; });
-          if (first_rc != kOk) return kOk;
-          bool ok = true;
-          if (bin) {
-            if (total) ok = fwrite(ids.data(), sizeof(int32_t), total, out) == total;
-            for (uint64_t s2 = 0; s2 < n_lines; ++s2) io[s2] += id_total;
-            if (n_lines) ok = ok && fwrite(io.data(), sizeof(uint64_t), n_lines, idx) == n_lines;
-          } else if (device_image) {
-            ok = image == 0 || fwrite(ws->h_text.p, 1, image, out) == image;
-          } else if (!formatted.empty()) {
-            ok = fwrite(formatted.data(), 1, formatted.size(), out) == formatted.size();
-          }
-          sent_total += n_lines;
-          id_total += total;
-          next_write = k + 1;
-          cv.notify_all();
-          if (!ok) return Fail(h, kDataLoss, "short write");
-        }
-        return kOk;
-      };
-      int rc = kOk;
-      try { rc = body(); } catch (const std::bad_alloc &) { rc = kResourceExhausted; t_error = "out of host memory"; } catch (...) { rc = kInternal; t_error = "unknown exception"; }
-      if (rc != kOk) {
-        const std::string err = t_error;
-        std::lock_guard<std::mutex> l(mu);
-        if (first_rc == kOk) { first_rc = rc; first_err = err; }
-        cv.notify_all();
-      }
+    const bool device_image = piece || (!bin && getenv("SPMX_ID_HOST_FORMAT") == nullptr);
+    MappedFile file;
+    if (int r = file.Open(h, in_path ? in_path : ""); r != kOk) return r;
+    const std::string out_name = out_path ? out_path : "";
+    OutFile out, idx;
+    if (!out.Open(out_name) || (bin && !idx.Open(out_name + ".idx"))) return Fail(h, kPermissionDenied, "cannot write \"" + out_name + "\"");
+    const std::vector<uint64_t> cut = CutAtLineEnds(file.p, file.size, FileChunkTarget());
+    uint64_t sent_total = 0, id_total = 0;
+    struct Scratch : TextChunk {
+      std::vector<int32_t> ids;
+      std::vector<uint64_t> io;
+      std::unique_ptr<char[]> lines;       // SPMX_ID_HOST_FORMAT: the image (new char[]: no page is touched before it is written)
+      uint64_t lines_cap = 0;
     };
-    std::vector<std::thread> pool;
-    for (int w = 1; w < T; ++w) pool.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : pool) t.join();
-    if (bin && first_rc == kOk) fwrite(&id_total, sizeof(uint64_t), 1, idx);      // the closing offset
-    if (idx) fclose(idx);
-    fclose(out);
-    if (file) munmap(const_cast<uint8_t *>(file), size);
-    if (first_rc != kOk) return Fail(h, first_rc, first_err);
+    auto process = [&](Scratch &s, uint64_t k) -> int {
+      TextChunk &c = s;
+      Workspace *ws = c.ws;
+      hipStream_t st = ws->stream;
+      if (int r = EncodeChunk(h, c, file.p + cut[k], cut[k + 1] - cut[k], piece); r != kOk) return r;
+      if (device_image) {                          // the finished image in one D2H
+        if (!piece) {
+          const int r = TokenText(h, ws, 0, true, ws->d_ids.p, ws->d_id_offs.p, c.n_lines, c.total, nullptr, nullptr, nullptr, 0, &ws->d_tt_out, st, &c.image);
+          if (r != kOk) return r;
+        }
+        HIP_OR_RETURN(h, ws->h_text.Reserve(c.image + 32));
+        if (c.image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, ws->d_tt_out.p, c.image, hipMemcpyDeviceToHost, st));
+        HIP_OR_RETURN(h, hipStreamSynchronize(st));
+        return kOk;
+      }
+      s.ids.resize(c.total);
+      s.io.resize(c.n_lines + 1);
+      if (c.total) HIP_OR_RETURN(h, hipMemcpyAsync(s.ids.data(), ws->d_ids.p, c.total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      HIP_OR_RETURN(h, hipMemcpyAsync(s.io.data(), ws->d_id_offs.p, (c.n_lines + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      HIP_OR_RETURN(h, hipStreamSynchronize(st));
+      if (!bin) {
+        const uint64_t cap = c.total * 11 + c.n_lines;
+        if (cap > s.lines_cap) { s.lines.reset(new char[cap]); s.lines_cap = cap; }
+        c.image = static_cast<uint64_t>(FormatIdLines(s.ids.data(), s.io.data(), c.n_lines, s.lines.get()) - s.lines.get());
+      }
+      return kOk;
+    };
+    auto commit = [&](Scratch &s, uint64_t) -> int {
+      const uint64_t n_lines = s.n_lines, total = s.total, image = s.image;
+      bool ok = true;
+      if (bin) {
+        if (total) ok = fwrite(s.ids.data(), sizeof(int32_t), total, out.f) == total;
+        for (uint64_t s2 = 0; s2 < n_lines; ++s2) s.io[s2] += id_total;
+        if (n_lines) ok = ok && fwrite(s.io.data(), sizeof(uint64_t), n_lines, idx.f) == n_lines;
+      } else if (image) {
+        ok = fwrite(device_image ? reinterpret_cast<const char *>(s.ws->h_text.p) : s.lines.get(), 1, image, out.f) == image;
+      }
+      sent_total += n_lines;
+      id_total += total;
+      return ok ? kOk : Fail(h, kDataLoss, "short write");
+    };
+    if (int rc = RunChunks<Scratch>(h, cut.size() - 1, true, process, commit); rc != kOk) return rc;
+    if (bin) fwrite(&id_total, sizeof(uint64_t), 1, idx.f);      // the closing offset
     if (n_sentences) *n_sentences = sent_total;
     if (n_ids) *n_ids = id_total;
     return kOk;
@@ -3902,122 +3939,36 @@ int spmx_count_ids_device(spmx_handle *h, const int32_t *d_ids, uint64_t n_ids, 
   });
 }
 
-/* The pipeline of spmx_encode_file with the count kernel in place of formatting: nothing comes back per chunk, the workers
- * share one device histogram (the kernel's adds to it are atomic) and the V + 1 words come back once, after the last chunk. */
+/* The chunk pipeline with the count kernel in place of formatting: nothing comes back per chunk and nothing is kept in
+ * order, the workers share one device histogram (the kernel's adds to it are atomic) and the V + 1 words come back once,
+ * after the last chunk. */
 int spmx_count_file(spmx_handle *h, const char *in_path, uint64_t *counts, uint64_t *n_sentences, uint64_t *n_ids) {
   if (!h) return kInvalidArgument;
   if (n_sentences) *n_sentences = 0;
   if (n_ids) *n_ids = 0;
   return Guard(h, [&]() -> int {
     if (!counts) return Fail(h, kInternal, "output container is null");
-    const int fd = open(in_path ? in_path : "", O_RDONLY);
-    if (fd < 0) return Fail(h, kNotFound, std::string("\"") + (in_path ? in_path : "") + "\": No such file or directory");
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) { close(fd); return Fail(h, kInternal, "fstat failed"); }
-    const uint64_t size = static_cast<uint64_t>(sb.st_size);
-    const uint8_t *file = nullptr;
-    if (size) {
-      void *m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m == MAP_FAILED) { close(fd); return Fail(h, kInternal, "mmap failed"); }
-      file = static_cast<const uint8_t *>(m);
-    }
-    close(fd);
-    struct Unmap { const uint8_t *p; uint64_t n; ~Unmap() { if (p) munmap(const_cast<uint8_t *>(p), n); } } unmap{file, size};
-    if (size == 0) return kOk;
-    // chunks of about 64 MiB that end after a line end
-    std::vector<uint64_t> cut(1, 0);
-    uint64_t target = 64ull << 20;
-    if (const char *e = getenv("SPMX_FILE_CHUNK")) {
-      const unsigned long long v = strtoull(e, nullptr, 10);
-      target = v < 4096 ? 4096 : v;
-    }
-    while (cut.back() < size) {
-      uint64_t e = cut.back() + target;
-      if (e >= size) e = size;
-      else {
-        const void *nl = memchr(file + e, '\n', size - e);
-        e = nl ? static_cast<uint64_t>(static_cast<const uint8_t *>(nl) - file) + 1 : size;
-      }
-      cut.push_back(e);
-    }
-    const uint64_t n_chunks = cut.size() - 1;
-    int T = h->host_threads < 4 ? h->host_threads : 4;
-    if (static_cast<uint64_t>(T) > n_chunks) T = static_cast<int>(n_chunks ? n_chunks : 1);
+    MappedFile file;
+    if (int r = file.Open(h, in_path ? in_path : ""); r != kOk) return r;
+    if (file.size == 0) return kOk;
+    const std::vector<uint64_t> cut = CutAtLineEnds(file.p, file.size, FileChunkTarget());
     const uint64_t V = h->model.pieces.size();
     HIP_OR_RETURN(h, hipSetDevice(h->device));
-    DevBuf<unsigned long long> d_hist;
-    struct Guard2 { DevBuf<unsigned long long> &b; ~Guard2() { b.Free(); } } gh{d_hist};
+    ScratchBuf<unsigned long long> d_hist;
     HIP_OR_RETURN(h, d_hist.Reserve(V + 1));
     HIP_OR_RETURN(h, hipMemset(d_hist.p, 0, (V + 1) * sizeof(unsigned long long)));
     HIP_OR_RETURN(h, hipDeviceSynchronize());         // (the workers' streams do not wait for the null stream)
-    std::mutex mu;
     uint64_t sent_total = 0, id_total = 0;
-    int first_rc = kOk;
-    std::string first_err;
-    auto worker = [&](int w) {
-      auto body = [&]() -> int {
-        HIP_OR_RETURN(h, hipSetDevice(h->device));
-        Lease L(h);
-        if (int r = L.Ready(); r != kOk) return r;
-        Workspace *ws = L.ws.get();
-        hipStream_t st = ws->stream;
-        DevBuf<uint8_t> d_file;
-        struct Guard3 { DevBuf<uint8_t> &b; ~Guard3() { b.Free(); } } g3{d_file};
-        for (uint64_t k = static_cast<uint64_t>(w); k < n_chunks; k += static_cast<uint64_t>(T)) {
-          { std::lock_guard<std::mutex> l(mu); if (first_rc != kOk) return kOk; }
-          const uint64_t bytes = cut[k + 1] - cut[k];
-          const uint8_t *src = file + cut[k];
-          uint64_t nl = 0;
-          for (const uint8_t *p = src, *e = src + bytes; p < e;) {
-            const void *q = memchr(p, '\n', static_cast<size_t>(e - p));
-            if (!q) break;
-            ++nl;
-            p = static_cast<const uint8_t *>(q) + 1;
-          }
-          const uint64_t lines = nl + (bytes && src[bytes - 1] != '\n' ? 1 : 0);
-          HIP_OR_RETURN(h, ws->h_text.Reserve(bytes + 32));
-          HIP_OR_RETURN(h, d_file.Reserve(bytes + 32));
-          HIP_OR_RETURN(h, ws->d_text.Reserve(bytes + 32));
-          HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 2));
-          HIP_OR_RETURN(h, ws->d_id_offs.Reserve(lines + 2));
-          memcpy(ws->h_text.p, src, bytes);
-          HIP_OR_RETURN(h, hipMemcpyAsync(d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
-          uint64_t n_lines = 0, text_bytes = 0;
-          int r = spmx_split_lines_device(h, d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &n_lines, &text_bytes);
-          if (r != kOk) return r;
-          uint64_t want = IdsGuess(h, text_bytes, n_lines), total = 0;
-          for (int attempt = 0; attempt < 2; ++attempt) {
-            HIP_OR_RETURN(h, ws->d_ids.Reserve(want));
-            r = EncodeDevice(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n_lines, ws->d_ids.p, ws->d_ids.cap, ws->d_id_offs.p,
-                             nullptr, st, &total, nullptr);
-            if (r != kResourceExhausted || total <= ws->d_ids.cap) break;
-            want = total;
-          }
-          if (r != kOk) return r;
-          if (total) {
-            r = CountIds(h, ws->d_ids.p, total, d_hist.p, st);
-            if (r != kOk) return r;
-          }
-          HIP_OR_RETURN(h, hipStreamSynchronize(st));     // (the staging buffer and the id arena are the next chunk's)
-          std::lock_guard<std::mutex> l(mu);
-          sent_total += n_lines;
-          id_total += total;
-        }
-        return kOk;
-      };
-      int rc = kOk;
-      try { rc = body(); } catch (const std::bad_alloc &) { rc = kResourceExhausted; t_error = "out of host memory"; } catch (...) { rc = kInternal; t_error = "unknown exception"; }
-      if (rc != kOk) {
-        const std::string err = t_error;
-        std::lock_guard<std::mutex> l(mu);
-        if (first_rc == kOk) { first_rc = rc; first_err = err; }
+    auto process = [&](TextChunk &c, uint64_t k) -> int {
+      if (int r = EncodeChunk(h, c, file.p + cut[k], cut[k + 1] - cut[k], false); r != kOk) return r;
+      if (c.total) {
+        if (int r = CountIds(h, c.ws->d_ids.p, c.total, d_hist.p, c.ws->stream); r != kOk) return r;
       }
+      HIP_OR_RETURN(h, hipStreamSynchronize(c.ws->stream));     // (the staging buffer and the id arena are the next chunk's)
+      return kOk;
     };
-    std::vector<std::thread> pool;
-    for (int w = 1; w < T; ++w) pool.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : pool) t.join();
-    if (first_rc != kOk) return Fail(h, first_rc, first_err);
+    auto commit = [&](TextChunk &c, uint64_t) -> int { sent_total += c.n_lines; id_total += c.total; return kOk; };
+    if (int rc = RunChunks<TextChunk>(h, cut.size() - 1, false, process, commit); rc != kOk) return rc;
     std::vector<unsigned long long> got(V + 1);
     HIP_OR_RETURN(h, hipMemcpy(got.data(), d_hist.p, (V + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i <= V; ++i) counts[i] += got[i];
@@ -4202,33 +4153,52 @@ int spmx_join_lines_device(spmx_handle *h, const void *d_text, const uint64_t *d
 
 
 /* ---- ids file -> corpus file (the caller-side loop of spm_decode, src/spm_decode_main.cc) -------------------------------
- * The inverse of spmx_encode_file, with the same pipeline of worker threads over chunks that end at a line end:
+ * The inverse of spmx_encode_file on the same chunk pipeline, a writer keeping the chunks in order:
  *   "id"     pinned staging copy -> H2D -> id-line parser -> Decode -> line joiner -> one D2H of the image -> fwrite
  *   "bin"    in_path: flat int32 ids, in_path + ".idx": n + 1 uint64 offsets; cut by offsets, then as above behind the parser
  *   "piece"  lines of space-separated pieces: PieceToId on the host (a piece outside the vocabulary travels as a literal, as
- *            in spmx_decode_batch_pieces), then Decode and the joiner
- * A writer keeps the chunks in order.  Of several failing chunks the lowest one's status is returned. */
+ *            in spmx_decode_batch_pieces), then Decode and the joiner */
 namespace {
-struct MappedFile {
-  const uint8_t *p = nullptr;
-  uint64_t size = 0;
-  // 0 ok, 1 cannot open, 2 other
-  int Open(const std::string &path) {
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return 1;
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) { close(fd); return 2; }
-    size = static_cast<uint64_t>(sb.st_size);
-    if (size) {
-      void *m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-      if (m == MAP_FAILED) { close(fd); size = 0; return 2; }
-      p = static_cast<const uint8_t *>(m);
-    }
-    close(fd);
-    return 0;
-  }
-  ~MappedFile() { if (p) munmap(const_cast<uint8_t *>(p), size); }
+struct DecodeChunk {                    // a worker's scratch
+  Workspace *ws = nullptr;
+  ScratchBuf<uint8_t> d_file, d_out;
+  std::vector<int32_t> ids;
+  std::vector<uint64_t> io;
+  std::vector<uint32_t> lit_offs;
+  std::string lit_bytes;
+  uint64_t lines = 0, total_ids = 0, image = 0;
+  ~DecodeChunk() { if (!ws) return; ws->lit_bytes = nullptr; ws->lit_offs = nullptr; ws->n_lit = 0; }
 };
+
+// std::getline and StrSplit(line, " ") without empty tokens, on the host; PieceToId per token
+int PiecesToIds(spmx_handle *h, bool to_unk, const uint8_t *p, const uint8_t *e, DecodeChunk &s) {
+  s.ids.clear(); s.io.assign(1, 0); s.lit_offs.assign(1, 0); s.lit_bytes.clear();
+  while (p < e) {
+    const uint8_t *nl = static_cast<const uint8_t *>(memchr(p, '\n', static_cast<size_t>(e - p)));
+    const uint8_t *le = nl ? nl : e;
+    while (p < le) {
+      if (*p == ' ') { ++p; continue; }
+      const uint8_t *sp = static_cast<const uint8_t *>(memchr(p, ' ', static_cast<size_t>(le - p)));
+      const uint8_t *te = sp ? sp : le;
+      const std::string tok(reinterpret_cast<const char *>(p), static_cast<size_t>(te - p));
+      int id = h->model.unk_id;
+      try { id = h->model.PieceToId(tok); } catch (...) {}
+      if (id == h->model.unk_id && tok != h->model.unk_piece && !to_unk) {
+        if (tok.size() > 0xFFFFu) return Fail(h, kInvalidArgument, "a piece outside the vocabulary is longer than 65535 bytes");
+        if (s.lit_offs.size() >= (1ull << 31) || s.lit_bytes.size() + tok.size() >= (1ull << 32))
+          return Fail(h, kInvalidArgument, "too many pieces outside the vocabulary in one batch");
+        s.lit_bytes += tok;
+        s.lit_offs.push_back(static_cast<uint32_t>(s.lit_bytes.size()));
+        id = -static_cast<int>(s.lit_offs.size() - 1);
+      }
+      s.ids.push_back(id);
+      p = te;
+    }
+    s.io.push_back(s.ids.size());
+    p = nl ? nl + 1 : e;
+  }
+  return kOk;
+}
 }  // namespace
 
 int spmx_decode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *input_format, uint64_t *n_lines,
@@ -4240,21 +4210,15 @@ int spmx_decode_file(spmx_handle *h, const char *in_path, const char *out_path, 
     const std::string fmt = input_format ? input_format : "id";
     const bool bin = fmt == "bin", piece = fmt == "piece";
     if (!bin && !piece && fmt != "id") return Fail(h, kInvalidArgument, "input_format must be \"id\", \"bin\" or \"piece\"");
-    uint64_t target = 64ull << 20;
-    if (const char *e = getenv("SPMX_FILE_CHUNK")) {
-      const unsigned long long v = strtoull(e, nullptr, 10);
-      target = v < 4096 ? 4096 : v;
-    }
+    const uint64_t target = FileChunkTarget();
     const std::string in = in_path ? in_path : "";
     MappedFile file, idx;
-    if (int r = file.Open(in); r != 0)
-      return r == 1 ? Fail(h, kNotFound, "\"" + in + "\": No such file or directory") : Fail(h, kInternal, "cannot map \"" + in + "\"");
+    if (int r = file.Open(h, in); r != kOk) return r;
     // chunk k: "id" / "piece" the bytes [cut[k], cut[k + 1]) of the file; "bin" the lines [cut[k], cut[k + 1])
     std::vector<uint64_t> cut(1, 0);
     const uint64_t *all_offs = nullptr;
     if (bin) {
-      if (int r = idx.Open(in + ".idx"); r != 0)
-        return r == 1 ? Fail(h, kNotFound, "\"" + in + ".idx\": No such file or directory") : Fail(h, kInternal, "cannot map \"" + in + ".idx\"");
+      if (int r = idx.Open(h, in + ".idx"); r != kOk) return r;
       if (idx.size < 8 || idx.size % 8 != 0) return Fail(h, kDataLoss, "\"" + in + ".idx\" does not hold n + 1 64-bit offsets");
       all_offs = reinterpret_cast<const uint64_t *>(idx.p);
       const uint64_t n = idx.size / 8 - 1;
@@ -4272,166 +4236,84 @@ int spmx_decode_file(spmx_handle *h, const char *in_path, const char *out_path, 
         cut.push_back(lo);
       }
     } else {
-      while (cut.back() < file.size) {
-        uint64_t e = cut.back() + target;
-        if (e >= file.size) e = file.size;
-        else {
-          const void *nl = memchr(file.p + e, '\n', file.size - e);
-          e = nl ? static_cast<uint64_t>(static_cast<const uint8_t *>(nl) - file.p) + 1 : file.size;
-        }
-        cut.push_back(e);
-      }
+      cut = CutAtLineEnds(file.p, file.size, target);
     }
-    FILE *out = fopen(out_path ? out_path : "", "wb");
-    if (!out) return Fail(h, kPermissionDenied, std::string("cannot write \"") + (out_path ? out_path : "") + "\"");
-    const uint64_t n_chunks = cut.size() - 1;
-    int T = h->host_threads < 4 ? h->host_threads : 4;
-    if (static_cast<uint64_t>(T) > n_chunks) T = static_cast<int>(n_chunks ? n_chunks : 1);
+    const std::string out_name = out_path ? out_path : "";
+    OutFile out;
+    if (!out.Open(out_name)) return Fail(h, kPermissionDenied, "cannot write \"" + out_name + "\"");
     bool to_unk = false;
     { std::lock_guard<std::mutex> l(h->mu); to_unk = h->dx_unk; }
-    std::mutex mu;
-    std::condition_variable cv;
-    uint64_t next_write = 0, line_total = 0, id_total = 0;
-    uint64_t fail_chunk = ~0ull;          // the lowest failing chunk so far, its status and text
-    int fail_rc = kOk;
-    std::string fail_err;
-    auto worker = [&](int w) {
-      uint64_t k = static_cast<uint64_t>(w);
-      auto body = [&]() -> int {
-        HIP_OR_RETURN(h, hipSetDevice(h->device));
-        Lease L(h);
-        if (int r = L.Ready(); r != kOk) return r;
-        Workspace *ws = L.ws.get();
-        hipStream_t st = ws->stream;
-        DevBuf<uint8_t> d_file, d_out;
-        struct Guard2 { DevBuf<uint8_t> &a, &b; ~Guard2() { a.Free(); b.Free(); } } g2{d_file, d_out};
-        struct LitGuard { Workspace *w; ~LitGuard() { w->lit_bytes = nullptr; w->lit_offs = nullptr; w->n_lit = 0; } } lit_guard{ws};
-        std::vector<int32_t> ids;
-        std::vector<uint64_t> io;
-        std::vector<uint32_t> lit_offs;
-        std::string lit_bytes;
-        for (; k < n_chunks; k += static_cast<uint64_t>(T)) {
-          { std::lock_guard<std::mutex> l(mu); if (fail_chunk < k) return kOk; }
-          const int32_t *d_ids = nullptr;      // the kernels address d_ids + offsets[i]
-          uint64_t lines = 0, total_ids = 0;
-          if (bin) {
-            const uint64_t l0 = cut[k], base = all_offs[l0];
-            lines = cut[k + 1] - l0;
-            total_ids = all_offs[cut[k + 1]] - base;
-            HIP_OR_RETURN(h, ws->d_ids.Reserve(total_ids + 16));
-            HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 1));
-            if (total_ids) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_ids.p, file.p + base * 4, total_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, all_offs + l0, (lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            d_ids = ws->d_ids.p - base;
-          } else if (piece) {
-            // std::getline and StrSplit(line, " ") without empty tokens, on the host; PieceToId per token
-            const uint8_t *p = file.p + cut[k], *e = file.p + cut[k + 1];
-            ids.clear(); io.assign(1, 0); lit_offs.assign(1, 0); lit_bytes.clear();
-            while (p < e) {
-              const uint8_t *nl = static_cast<const uint8_t *>(memchr(p, '\n', static_cast<size_t>(e - p)));
-              const uint8_t *le = nl ? nl : e;
-              while (p < le) {
-                if (*p == ' ') { ++p; continue; }
-                const uint8_t *sp = static_cast<const uint8_t *>(memchr(p, ' ', static_cast<size_t>(le - p)));
-                const uint8_t *te = sp ? sp : le;
-                const std::string tok(reinterpret_cast<const char *>(p), static_cast<size_t>(te - p));
-                int id = h->model.unk_id;
-                try { id = h->model.PieceToId(tok); } catch (...) {}
-                if (id == h->model.unk_id && tok != h->model.unk_piece && !to_unk) {
-                  if (tok.size() > 0xFFFFu) return Fail(h, kInvalidArgument, "a piece outside the vocabulary is longer than 65535 bytes");
-                  if (lit_offs.size() >= (1ull << 31) || lit_bytes.size() + tok.size() >= (1ull << 32))
-                    return Fail(h, kInvalidArgument, "too many pieces outside the vocabulary in one batch");
-                  lit_bytes += tok;
-                  lit_offs.push_back(static_cast<uint32_t>(lit_bytes.size()));
-                  id = -static_cast<int>(lit_offs.size() - 1);
-                }
-                ids.push_back(id);
-                p = te;
-              }
-              io.push_back(ids.size());
-              p = nl ? nl + 1 : e;
-            }
-            lines = io.size() - 1;
-            total_ids = ids.size();
-            const uint32_t n_lit = static_cast<uint32_t>(lit_offs.size() - 1);
-            HIP_OR_RETURN(h, ws->d_ids.Reserve(total_ids + 16));
-            HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 1));
-            if (total_ids) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_ids.p, ids.data(), total_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, io.data(), (lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            ws->lit_bytes = nullptr; ws->lit_offs = nullptr; ws->n_lit = 0;
-            if (n_lit) {
-              HIP_OR_RETURN(h, ws->d_lit_offs.Reserve(n_lit + 1));
-              HIP_OR_RETURN(h, ws->d_lit_bytes.Reserve(lit_bytes.size() + 16));
-              HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_lit_offs.p, lit_offs.data(), (n_lit + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-              if (!lit_bytes.empty()) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_lit_bytes.p, lit_bytes.data(), lit_bytes.size(), hipMemcpyHostToDevice, st));
-              ws->lit_bytes = ws->d_lit_bytes.p; ws->lit_offs = ws->d_lit_offs.p; ws->n_lit = n_lit;
-            }
-            HIP_OR_RETURN(h, hipStreamSynchronize(st));        // (the vectors are reused by the next chunk)
-            d_ids = ws->d_ids.p;
-          } else {
-            const uint64_t bytes = cut[k + 1] - cut[k];
-            HIP_OR_RETURN(h, ws->h_text.Reserve(bytes + 32));
-            HIP_OR_RETURN(h, d_file.Reserve(bytes + 32));
-            memcpy(ws->h_text.p, file.p + cut[k], bytes);
-            HIP_OR_RETURN(h, hipMemcpyAsync(d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
-            // a token takes two bytes at least but for the image's last one; the lines are a guess the parser corrects
-            HIP_OR_RETURN(h, ws->d_ids.Reserve(bytes / 2 + 16));
-            uint64_t want_offs = bytes / 8 + 1024;
-            int r = kOk;
-            for (int attempt = 0; attempt < 2; ++attempt) {
-              HIP_OR_RETURN(h, ws->d_offs.Reserve(want_offs));
-              r = ParseIdLines(h, ws, d_file.p, bytes, ws->d_ids.p, ws->d_ids.cap, ws->d_offs.p, ws->d_offs.cap, st, &lines, &total_ids);
-              if (r != kResourceExhausted || lines + 1 <= ws->d_offs.cap) break;
-              want_offs = lines + 1;
-            }
-            if (r != kOk) return r;
-            d_ids = ws->d_ids.p;
-          }
-          // Decode -> joiner -> one D2H of the finished image
-          HIP_OR_RETURN(h, ws->d_id_offs.Reserve(lines + 1));
-          uint64_t cap = total_ids * 6 + 64, text_bytes = 0;
-          int r = kOk;
-          for (int attempt = 0; attempt < 2; ++attempt) {
-            HIP_OR_RETURN(h, ws->d_text.Reserve(cap));
-            r = DecodeDevice(h, ws, d_ids, ws->d_offs.p, lines, ws->d_text.p, ws->d_text.cap, ws->d_id_offs.p, st, &text_bytes);
-            if (r != kResourceExhausted || text_bytes <= ws->d_text.cap) break;
-            cap = text_bytes;
-          }
-          if (r != kOk) return r;
-          uint64_t image = 0;
-          HIP_OR_RETURN(h, d_out.Reserve(text_bytes + lines + 32));
-          r = JoinLines(h, ws->d_text.p, ws->d_id_offs.p, lines, d_out.p, d_out.cap, st, &image, &text_bytes);
-          if (r != kOk) return r;
-          HIP_OR_RETURN(h, ws->h_text.Reserve(image + 32));
-          if (image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, d_out.p, image, hipMemcpyDeviceToHost, st));
-          HIP_OR_RETURN(h, hipStreamSynchronize(st));
-          std::unique_lock<std::mutex> l(mu);
-          cv.wait(l, [&] { return next_write == k || fail_chunk < k; });
-          if (fail_chunk < k) return kOk;
-          const bool ok = image == 0 || fwrite(ws->h_text.p, 1, image, out) == image;
-          line_total += lines;
-          id_total += total_ids;
-          next_write = k + 1;
-          cv.notify_all();
-          if (!ok) return Fail(h, kDataLoss, "short write");
+    uint64_t line_total = 0, id_total = 0;
+    auto process = [&](DecodeChunk &s, uint64_t k) -> int {
+      Workspace *ws = s.ws;
+      hipStream_t st = ws->stream;
+      const int32_t *d_ids = nullptr;      // the kernels address d_ids + offsets[i]
+      uint64_t &lines = s.lines, &total_ids = s.total_ids;
+      lines = total_ids = s.image = 0;
+      if (bin) {
+        const uint64_t l0 = cut[k], base = all_offs[l0];
+        lines = cut[k + 1] - l0;
+        total_ids = all_offs[cut[k + 1]] - base;
+        HIP_OR_RETURN(h, ws->d_ids.Reserve(total_ids + 16));
+        HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 1));
+        if (total_ids) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_ids.p, file.p + base * 4, total_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, all_offs + l0, (lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        d_ids = ws->d_ids.p - base;
+      } else if (piece) {
+        if (int r = PiecesToIds(h, to_unk, file.p + cut[k], file.p + cut[k + 1], s); r != kOk) return r;
+        lines = s.io.size() - 1;
+        total_ids = s.ids.size();
+        const uint32_t n_lit = static_cast<uint32_t>(s.lit_offs.size() - 1);
+        HIP_OR_RETURN(h, ws->d_ids.Reserve(total_ids + 16));
+        HIP_OR_RETURN(h, ws->d_offs.Reserve(lines + 1));
+        if (total_ids) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_ids.p, s.ids.data(), total_ids * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, s.io.data(), (lines + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        ws->lit_bytes = nullptr; ws->lit_offs = nullptr; ws->n_lit = 0;
+        if (n_lit) {
+          HIP_OR_RETURN(h, ws->d_lit_offs.Reserve(n_lit + 1));
+          HIP_OR_RETURN(h, ws->d_lit_bytes.Reserve(s.lit_bytes.size() + 16));
+          HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_lit_offs.p, s.lit_offs.data(), (n_lit + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+          if (!s.lit_bytes.empty()) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_lit_bytes.p, s.lit_bytes.data(), s.lit_bytes.size(), hipMemcpyHostToDevice, st));
+          ws->lit_bytes = ws->d_lit_bytes.p; ws->lit_offs = ws->d_lit_offs.p; ws->n_lit = n_lit;
         }
-        return kOk;
-      };
-      int rc = kOk;
-      try { rc = body(); } catch (const std::bad_alloc &) { rc = kResourceExhausted; t_error = "out of host memory"; } catch (...) { rc = kInternal; t_error = "unknown exception"; }
-      if (rc != kOk) {
-        const std::string err = t_error;
-        std::lock_guard<std::mutex> l(mu);
-        if (k < fail_chunk) { fail_chunk = k; fail_rc = rc; fail_err = err; }
-        cv.notify_all();
+        HIP_OR_RETURN(h, hipStreamSynchronize(st));        // (the vectors are reused by the next chunk)
+        d_ids = ws->d_ids.p;
+      } else {
+        const uint64_t bytes = cut[k + 1] - cut[k];
+        HIP_OR_RETURN(h, ws->h_text.Reserve(bytes + 32));
+        HIP_OR_RETURN(h, s.d_file.Reserve(bytes + 32));
+        memcpy(ws->h_text.p, file.p + cut[k], bytes);
+        HIP_OR_RETURN(h, hipMemcpyAsync(s.d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
+        // a token takes two bytes at least but for the image's last one; the lines are a guess the parser corrects
+        HIP_OR_RETURN(h, ws->d_ids.Reserve(bytes / 2 + 16));
+        const int r = GrowOnce(h, ws->d_offs, bytes / 8 + 1024, &lines, 1, [&] {       // (lines + 1 offsets)
+          return ParseIdLines(h, ws, s.d_file.p, bytes, ws->d_ids.p, ws->d_ids.cap, ws->d_offs.p, ws->d_offs.cap, st, &lines, &total_ids);
+        });
+        if (r != kOk) return r;
+        d_ids = ws->d_ids.p;
       }
+      // Decode -> joiner -> one D2H of the finished image
+      HIP_OR_RETURN(h, ws->d_id_offs.Reserve(lines + 1));
+      uint64_t text_bytes = 0;
+      int r = GrowOnce(h, ws->d_text, total_ids * 6 + 64, &text_bytes, 0, [&] {
+        return DecodeDevice(h, ws, d_ids, ws->d_offs.p, lines, ws->d_text.p, ws->d_text.cap, ws->d_id_offs.p, st, &text_bytes);
+      });
+      if (r != kOk) return r;
+      HIP_OR_RETURN(h, s.d_out.Reserve(text_bytes + lines + 32));
+      r = JoinLines(h, ws->d_text.p, ws->d_id_offs.p, lines, s.d_out.p, s.d_out.cap, st, &s.image, &text_bytes);
+      if (r != kOk) return r;
+      HIP_OR_RETURN(h, ws->h_text.Reserve(s.image + 32));
+      if (s.image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, s.d_out.p, s.image, hipMemcpyDeviceToHost, st));
+      HIP_OR_RETURN(h, hipStreamSynchronize(st));
+      return kOk;
     };
-    std::vector<std::thread> pool;
-    for (int w = 1; w < T; ++w) pool.emplace_back(worker, w);
-    worker(0);
-    for (auto &t : pool) t.join();
-    fclose(out);
-    if (fail_rc != kOk) return Fail(h, fail_rc, fail_err);
+    auto commit = [&](DecodeChunk &s, uint64_t) -> int {
+      const bool ok = s.image == 0 || fwrite(s.ws->h_text.p, 1, s.image, out.f) == s.image;
+      line_total += s.lines;
+      id_total += s.total_ids;
+      return ok ? kOk : Fail(h, kDataLoss, "short write");
+    };
+    if (int rc = RunChunks<DecodeChunk>(h, cut.size() - 1, true, process, commit); rc != kOk) return rc;
     if (n_lines) *n_lines = line_total;
     if (n_ids) *n_ids = id_total;
     return kOk;

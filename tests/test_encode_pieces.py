@@ -253,6 +253,23 @@ def test_pieces_capacity_protocol(emu):
     assert (pb[nbytes:] == 0xCD).all() and po[total] == nbytes and po[total + 1] == 0xCDCDCDCD
     want = h.sp.EncodePiecesPacked(text[:int(offs[n])], offs)
     assert np.array_equal(ids, want[0]) and pb[:nbytes].tobytes() == want[2].tobytes() and np.array_equal(po[:total + 1], want[3])
+    # one id short: the exact need again, and at that need the same result
+    ids2 = np.zeros(total, dtype=np.int32)
+    assert call(ids2, total - 1, pb, nbytes, po) == 8 and ti.value == total
+    assert call(ids2, total, pb, nbytes, po) == 0 and np.array_equal(ids2, want[0]) and pb[:nbytes].tobytes() == want[2].tobytes()
+    # the way back, spmx_decode_batch_device: one byte short, then at the reported need
+    dids = np.concatenate([ids, np.zeros(16, dtype=np.int32)])
+    text_want, toffs_want = h.sp.DecodePacked(ids, io)
+    assert text_want.tobytes() == b"Hello world.I saw a girl with a telescope." and toffs_want.tolist() == [0, 12, 12, 42]
+    need, to = C.c_uint64(0), np.zeros(n + 1, dtype=np.uint64)
+    buf = np.full(len(text_want) + 16, 0xCD, dtype=np.uint8)
+
+    def decode(cap):
+        return h.lib.spmx_decode_batch_device(h.sp._h, dids.ctypes.data, io.ctypes.data, n, buf.ctypes.data, cap, to.ctypes.data, None,
+                                              C.byref(need))
+    assert decode(len(text_want) - 1) == 8 and need.value == len(text_want)
+    assert decode(need.value) == 0, h.lib.spmx_last_error(None)
+    assert buf[:need.value].tobytes() == text_want.tobytes() and (buf[need.value:] == 0xCD).all() and np.array_equal(to, toffs_want)
     # n == 0: an empty result
     assert h.lib.spmx_encode_batch_pieces_device(h.sp._h, None, 0, offs.ctypes.data, 0, None, 0, io.ctypes.data, None, 0, po.ctypes.data,
                                                  None, C.byref(ti), C.byref(tb)) == 0

@@ -98,6 +98,146 @@ def test_emu_encode_file(emu, tmp_path):
     assert [int(x) for x in lines[7].split()] == ids[int(io[7]):int(io[8])].tolist()
 
 
+BOTCHAN = os.path.join(fixtures.GOLDEN, "botchan.txt")
+
+
+def read_bin(path):
+    return np.fromfile(path, dtype=np.int32), np.fromfile(path + ".idx", dtype=np.uint64)
+
+
+def count_file(sp, path):
+    """spmx_count_file -> (status, counts, n_sentences, n_ids)."""
+    counts = np.zeros(sp.GetPieceSize() + 1, dtype=np.uint64)
+    ns, ni = C.c_uint64(0), C.c_uint64(0)
+    rc = sp._lib.spmx_count_file(sp._h, path.encode(), counts.ctypes.data, C.byref(ns), C.byref(ni))
+    return rc, counts, ns.value, ni.value
+
+
+@pytest.fixture(scope="module")
+def botchan_one_chunk(emu, tmp_path_factory):
+    """botchan.txt as one chunk: (ids, offsets) of format "bin" and the histogram of spmx_count_file."""
+    sp = emu.load(fixtures.model_blob("test_model"), classes=None).sp
+    out = str(tmp_path_factory.mktemp("one_chunk") / "ids.bin")
+    assert "SPMX_FILE_CHUNK" not in os.environ
+    assert sp.EncodeFile(BOTCHAN, out, "bin") == (4288, 95515)
+    rc, counts, ns, ni = count_file(sp, BOTCHAN)
+    assert (rc, ns, ni) == (0, 4288, 95515) and int(counts.sum()) == 95515
+    return read_bin(out) + (counts,)
+
+
+def check_chunked_file_calls(sp, want, tmp_path):
+    """Formats "id" and "bin" and the histogram, SPMX_FILE_CHUNK set by the caller: what one chunk gives."""
+    ids, io, counts = want
+    out, outb = str(tmp_path / "ids.txt"), str(tmp_path / "ids.bin")
+    assert sp.EncodeFile(BOTCHAN, out, "id") == (4288, 95515)
+    assert hashlib.md5(open(out, "rb").read()).hexdigest() == BOTCHAN_ID_MD5
+    assert sp.EncodeFile(BOTCHAN, outb, "bin") == (4288, 95515)
+    got_ids, got_io = read_bin(outb)
+    np.testing.assert_array_equal(got_io, io)
+    np.testing.assert_array_equal(got_ids, ids)
+    rc, got, ns, ni = count_file(sp, BOTCHAN)
+    assert (rc, ns, ni) == (0, 4288, 95515)
+    np.testing.assert_array_equal(got, counts)
+
+
+@pytest.mark.parametrize("threads", ["1", "4"])
+def test_emu_file_calls_chunked(threads, emu, botchan_one_chunk, tmp_path, monkeypatch):
+    """More than 50 chunks of 4 KiB through one worker and through four: spmx_encode_file's "id" (on the device and on the
+    host's formatting loop) and "bin" and spmx_count_file give what one chunk gives."""
+    sp = emu.load(fixtures.model_blob("test_model"), classes=None, env={"SPMX_HOST_THREADS": threads}).sp
+    assert os.path.getsize(BOTCHAN) > 50 * 4096
+    monkeypatch.setenv("SPMX_FILE_CHUNK", "4096")
+    check_chunked_file_calls(sp, botchan_one_chunk, tmp_path)
+    monkeypatch.setenv("SPMX_ID_HOST_FORMAT", "1")
+    out = str(tmp_path / "ids_host.txt")
+    assert sp.EncodeFile(BOTCHAN, out, "id") == (4288, 95515)
+    assert hashlib.md5(open(out, "rb").read()).hexdigest() == BOTCHAN_ID_MD5
+
+
+def test_emu_file_calls_second_attempt(emu, oracle, tmp_path):
+    """The grow-and-retry helper's second attempt inside the file calls, made certain: lines of punctuation give about
+    one id per byte, more than the id arena holds after its first reservation (the guess of one id per two bytes and 4 per
+    line + 64, a quarter and 79 on top at the most), so the encode runs again at the reported need.  A fresh handle per
+    call: a workspace keeps what it has grown to."""
+    blob = fixtures.model_blob("test_model")
+    lines = [b";.,!" * 60, b",;" * 300, b"Hello world.", b"!.;," * 150]
+    text = np.frombuffer(b"".join(lines), dtype=np.uint8)
+    offs = np.cumsum([0] + [len(x) for x in lines]).astype(np.uint64)
+    oids, oio = oracle.load(blob).encode_batch(text, offs)
+    guess = len(text) // 2 + 4 * len(lines) + 64
+    assert len(oids) > guess + guess // 4 + 79
+    sp = emu.load(blob, classes=None).sp
+    src, out = str(tmp_path / "punct.txt"), str(tmp_path / "punct.bin")
+    with open(src, "wb") as f:
+        f.write(b"\n".join(lines) + b"\n")
+    assert sp.EncodeFile(src, out, "bin") == (len(lines), len(oids))
+    ids, io = read_bin(out)
+    np.testing.assert_array_equal(io, oio)
+    np.testing.assert_array_equal(ids, oids)
+    rc, counts, ns, ni = count_file(emu.load(blob, classes=None).sp, src)
+    assert (rc, ns, ni) == (0, len(lines), len(oids))
+    np.testing.assert_array_equal(counts[:-1], np.bincount(oids, minlength=sp.GetPieceSize()))
+
+
+def test_emu_file_call_failures(emu, tmp_path):
+    """A missing input and an output that cannot be opened, ten times each: the status and text, no descriptor left open,
+    and the handle encodes the file afterwards (nothing left locked or leased)."""
+    sp = emu.load(fixtures.model_blob("test_model"), classes=None, env={"SPMX_HOST_THREADS": "4"}).sp
+    lib, missing, nodir = sp._lib, str(tmp_path / "nothing"), str(tmp_path / "no_such_dir" / "out")
+    ns, ni = C.c_uint64(0), C.c_uint64(0)
+    counts = np.ones(sp.GetPieceSize() + 1, dtype=np.uint64)
+    head, head_out = str(tmp_path / "head.txt"), str(tmp_path / "head.ids")
+    with open(head, "wb") as f:
+        f.write(b"".join(open(BOTCHAN, "rb").readlines()[:40]))
+    assert sp.EncodeFile(head, head_out, "id")[0] == 40
+    head_want = open(head_out, "rb").read()
+    assert head_want.count(b"\n") == 40
+
+    def works():
+        assert sp.EncodeFile(head, head_out, "id")[0] == 40 and open(head_out, "rb").read() == head_want
+
+    def failing_calls():
+        for fmt in (b"id", b"piece", b"bin"):
+            assert lib.spmx_encode_file(sp._h, missing.encode(), str(tmp_path / "o").encode(), fmt, C.byref(ns), C.byref(ni)) == 5
+            assert lib.spmx_last_error(sp._h).decode() == '"%s": No such file or directory' % missing
+            works()
+            assert lib.spmx_encode_file(sp._h, BOTCHAN.encode(), nodir.encode(), fmt, C.byref(ns), C.byref(ni)) == 7
+            assert lib.spmx_last_error(sp._h).decode() == 'cannot write "%s"' % nodir
+            works()
+        assert count_file(sp, missing)[0] == 5
+        assert lib.spmx_last_error(sp._h).decode() == '"%s": No such file or directory' % missing
+        works()
+        assert lib.spmx_write_vocabulary(sp._h, counts.ctypes.data, nodir.encode(), C.byref(ns)) == 7
+        assert lib.spmx_last_error(sp._h).decode() == 'cannot write "%s"' % nodir
+        works()
+    failing_calls()                               # (whatever the first calls open for good is open now)
+    fds = len(os.listdir("/proc/self/fd")) if os.path.isdir("/proc/self/fd") else None
+    for _ in range(10):
+        failing_calls()
+    if fds is not None:
+        assert len(os.listdir("/proc/self/fd")) == fds
+    out = str(tmp_path / "ids.txt")
+    assert sp.EncodeFile(BOTCHAN, out, "id") == (4288, 95515)
+    assert hashlib.md5(open(out, "rb").read()).hexdigest() == BOTCHAN_ID_MD5
+    rc, got, n_sent, n_ids = count_file(sp, BOTCHAN)
+    assert (rc, n_sent, n_ids, int(got.sum())) == (0, 4288, 95515, 95515)
+
+
+@pytest.mark.gpu
+def test_gpu_file_calls_chunked(tmp_path, monkeypatch):
+    """test_emu_file_calls_chunked on the device, four workers on four streams: the order of the chunks in the output."""
+    from sentencepiece_amd.processor import SentencePieceProcessor
+    model = os.path.join(fixtures.GOLDEN, "test_model.model")
+    monkeypatch.setenv("SPMX_HOST_THREADS", "4")
+    sp = SentencePieceProcessor(model_file=model)
+    outb = str(tmp_path / "one.bin")
+    assert sp.EncodeFile(BOTCHAN, outb, "bin") == (4288, 95515)
+    rc, counts, ns, ni = count_file(sp, BOTCHAN)
+    assert (rc, ns, ni) == (0, 4288, 95515)
+    monkeypatch.setenv("SPMX_FILE_CHUNK", "4096")
+    check_chunked_file_calls(sp, read_bin(outb) + (counts,), tmp_path)
+
+
 @pytest.mark.gpu
 def test_gpu_encode_file_and_cli(tmp_path):
     """The same known answer on the GPU, through the Python wrapper and through the spmx_encode command line."""
