@@ -9,6 +9,7 @@ id below comes from the reference compiled from /root/reference.
 
     python scripts/make_fixtures.py            # everything
     python scripts/make_fixtures.py --only ids # just re-generate golden ids
+    python scripts/make_fixtures.py --only rulesets  # just the four rule-set models (needs only the wheel)
 """
 import argparse
 import hashlib
@@ -104,6 +105,19 @@ def make_models():
     train("uni32k", sample, model_type="unigram", **common)
     train("bpe32k", sample, model_type="bpe", **common)
     os.remove(sample)
+    make_ruleset_models()
+
+
+RULESET_MODELS = [("uni1k_nfkc", "unigram", "nfkc"), ("uni1k_cf", "unigram", "nmt_nfkc_cf"),
+                  ("bpe1k_cf", "bpe", "nmt_nfkc_cf"), ("uni1k_nfkc_cf", "unigram", "nfkc_cf")]
+
+
+def make_ruleset_models():
+    """One small model per built-in rule set that no other fixture carries (nmt_nfkc is everywhere): what
+    tests/test_charsmap_sweep.py sweeps key by key.  Almost all of each file is the rule set's charsmap."""
+    bot = f"{G}/botchan.txt"
+    for name, model_type, rule in RULESET_MODELS:
+        train(name, bot, vocab_size=1000, model_type=model_type, normalization_rule_name=rule, num_threads=1)
 
 
 def corpora():
@@ -243,8 +257,10 @@ def make_spans():
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["models", "ids", "spans"], default=None)
+    ap.add_argument("--only", choices=["models", "rulesets", "ids", "spans"], default=None)
     a = ap.parse_args()
+    if a.only == "rulesets":
+        make_ruleset_models()
     if a.only in (None, "models"):
         make_models()
     if a.only in (None, "ids"):

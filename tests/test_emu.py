@@ -53,7 +53,8 @@ def test_emu_long_sentences(model, emu, oracle, corpora):
         np.testing.assert_array_equal(ids, oids)
 
 
-@pytest.mark.parametrize("model", ["c5_250k", "test_ja_model", "uni1k_bf", "bpe32k", "uni1k_ident", "bpe1k_llama"])
+@pytest.mark.parametrize("model", ["c5_250k", "test_ja_model", "uni1k_bf", "bpe32k", "uni1k_ident", "bpe1k_llama",
+                                   "uni1k_nfkc", "uni1k_cf", "bpe1k_cf", "uni1k_nfkc_cf"])
 @pytest.mark.parametrize("mode", ["always", "never", "auto"])
 def test_emu_normalizer_forms(model, mode, emu, oracle, corpora):
     """The three lane normalizers of the streaming kernels give the reference's text: the byte-stepping form that

@@ -10,7 +10,8 @@ from sentencepiece_amd import synth
 from tests import fixtures, refshim
 
 MODELS = ["test_model", "test_ja_model", "uni1k_bf", "uni1k_uds", "uni1k_ident", "uni1k_suffix", "bpe1k", "bpe1k_bf_uds",
-          "bpe1k_noesc", "uni32k", "bpe32k", "c5_250k_bf", "bpe1k_llama"]
+          "bpe1k_noesc", "uni32k", "bpe32k", "c5_250k_bf", "bpe1k_llama",
+          "uni1k_nfkc", "uni1k_cf", "bpe1k_cf", "uni1k_nfkc_cf"]      # (the rule sets no other fixture carries: case folding)
 
 
 def fuzz_corpus(n, seed, corpora):
