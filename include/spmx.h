@@ -449,6 +449,42 @@ int spmx_sample_encode_and_score_batch_spans(spmx_handle *h, const char *text, c
                                              uint64_t **result_offsets, uint32_t **begin, uint32_t **end,
                                              uint32_t **nbegin, uint32_t **nend);
 
+/* ---- the lattice calls on device buffers ------------------------------------
+ * NBestEncode with the text and every result on the device: the search as spmx_nbest_encode_batch runs it, then its sparse
+ * results go to a dense CSR on the device (kernels_latticecsr.h) -- nothing but a few counters crosses to the host.  Input
+ * as spmx_encode_batch_device.  Output, the rows spmx_nbest_encode_batch returns, in the caller's device memory: sentence s
+ * owns the results [d_result_offsets[s], d_result_offsets[s + 1]) (n + 1 entries), best first; result r is
+ * d_ids[d_id_offsets[r], d_id_offsets[r + 1]) with d_scores[r], and d_sent_of_result[r] (may be NULL) is its sentence.
+ * d_id_offsets holds results_capacity + 1 entries, d_scores and d_sent_of_result results_capacity.  The buffers may have
+ * any alignment their element type allows.
+ * Capacity protocol of spmx_encode_batch_pieces_device: too small a results_capacity or ids_capacity ->
+ * RESOURCE_EXHAUSTED (8) with *total_results and *total_ids set and nothing written outside the buffers; NULL buffers with
+ * capacity 0 ask for the sizes.  A model that is not unigram: INTERNAL "NBestEncode is not available for the current
+ * model."; nbest_size 1 (and n == 0) is the plain encoder, score 0, one result per sentence. */
+int spmx_nbest_encode_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets,
+                                   uint64_t n, int nbest_size, int32_t *d_ids, uint64_t ids_capacity, uint64_t *d_id_offsets,
+                                   float *d_scores, uint32_t *d_sent_of_result, uint64_t results_capacity,
+                                   uint64_t *d_result_offsets, void *stream, uint64_t *total_results, uint64_t *total_ids);
+/* SampleEncode on device buffers, every branch of spmx_sample_encode_batch: lattice sampling (nbest_size < 0), the plain
+ * encoder (0 or 1), one of the nbest_size best drawn on the device (> 1), BPE-dropout for BPE models (alpha <= 0: the plain
+ * encoder); the refusals are the host call's.  One result per sentence: d_id_offsets holds n + 1 entries.  The draws of
+ * sentence s are keyed by (seed, index_base + s): sentences [k, n) of a batch, run with index_base = k, give the rows k..n
+ * of the whole batch -- a corpus may be cut anywhere.  index_base 0 gives what spmx_sample_encode_batch gives, but for
+ * nbest_size > 1, where a draw within one rounding of exp() of a boundary between two results may fall on the other side
+ * (the device's exp against glibc's).  Capacity protocol as spmx_encode_batch_device. */
+int spmx_sample_encode_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets,
+                                    uint64_t n, int nbest_size, float alpha, uint64_t seed, uint64_t index_base,
+                                    int32_t *d_ids, uint64_t ids_capacity, uint64_t *d_id_offsets, void *stream,
+                                    uint64_t *total_ids);
+/* SampleEncodeAndScore on device buffers: arguments and refusals of spmx_sample_encode_and_score_batch, outputs and
+ * capacity protocol of spmx_nbest_encode_batch_device.  A sentence without a result owns an empty range. */
+int spmx_sample_encode_and_score_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes,
+                                              const uint64_t *d_offsets, uint64_t n, int num_samples, float alpha, int wor,
+                                              int include_best, uint64_t seed, int32_t *d_ids, uint64_t ids_capacity,
+                                              uint64_t *d_id_offsets, float *d_scores, uint32_t *d_sent_of_result,
+                                              uint64_t results_capacity, uint64_t *d_result_offsets, void *stream,
+                                              uint64_t *total_results, uint64_t *total_ids);
+
 /* The reference's ORIGINAL unigram encoder (EncoderVersion::kOriginal, src/unigram_model.cc:674-692): the lattice of
  * Lattice::SetSentence / Model::PopulateNodes and Lattice::Viterbi (:161-198, all-float, first best left node wins)
  * instead of EncodeOptimized.  Same ids except where float and double arithmetic break a tie differently. */
@@ -476,6 +512,19 @@ int spmx_split_lines_device(spmx_handle *h, const void *d_file, uint64_t bytes, 
  * that fails by itself has no ids and becomes an empty line. */
 int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, const char *format, uint64_t *n_sentences,
                      uint64_t *n_ids);
+/* spmx_encode_file with the lattice formats of spm_encode (src/spm_encode_main.cc:120-153).  "id", "piece" and "bin" are
+ * spmx_encode_file's, byte for byte.  "nbest_id" / "nbest_piece": NBestEncode(line, nbest_size) per input line, one output
+ * line of ids / of pieces per result, best first (:136-149; unigram models only, INTERNAL otherwise as the reference).
+ * "sample_id" / "sample_piece": SampleEncode(line, nbest_size, alpha) per input line, one output line (:122-131), every branch of
+ * spmx_sample_encode_batch_device; the draws of a line are keyed by (seed, its line number in the file) alone, whatever
+ * SPMX_FILE_CHUNK is and however many workers run, and equal spmx_sample_encode_batch's over the file's lines with the same
+ * seed.  "proto", "sample_proto", "nbest_proto": the reference encodes and writes nothing; here out_path is left empty
+ * without encoding.  Pieces are what NBestEncodeAsPieces / SampleEncodeAsPieces give, the encode extra options (bos, eos,
+ * reverse, unk_piece) included.  *n_sentences counts input lines, *n_lines output lines, *n_ids the ids (pieces) written;
+ * any of them may be NULL.  Ids and pieces reach the file through the device's token-text writer over the result CSR, one
+ * D2H of the finished image per chunk. */
+int spmx_encode_file_ex(spmx_handle *h, const char *in_path, const char *out_path, const char *format, int nbest_size,
+                        float alpha, uint64_t seed, uint64_t *n_sentences, uint64_t *n_lines, uint64_t *n_ids);
 
 /* ---- corpus file side of Decode ------------------------------------------
  * The caller-side steps of the reference's spm_decode (src/spm_decode_main.cc: std::getline, StrSplit(line, " ") without

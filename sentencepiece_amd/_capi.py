@@ -113,6 +113,8 @@ SYMBOLS = [
       C.c_void_p, C.c_void_p]),
     ("spmx_packed_status", C.c_int, [C.c_void_p]),
     ("spmx_encode_file", C.c_int, [_H, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_U64), C.POINTER(_U64)]),
+    ("spmx_encode_file_ex", C.c_int,
+     [_H, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_float, _U64, C.POINTER(_U64), C.POINTER(_U64), C.POINTER(_U64)]),
     ("spmx_sample_encode_batch", C.c_int,
      [_H, C.c_void_p, C.c_void_p, _U64, C.c_int, C.c_float, _U64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("spmx_calculate_entropy_batch", C.c_int, [_H, C.c_void_p, C.c_void_p, _U64, C.c_float, C.POINTER(C.c_void_p)]),
@@ -120,6 +122,15 @@ SYMBOLS = [
      [_H, C.c_void_p, C.c_void_p, _U64, C.c_int, C.c_float, C.c_int, C.c_int, _U64] + [C.POINTER(C.c_void_p)] * 4),
     ("spmx_sample_encode_and_score_batch_spans", C.c_int,
      [_H, C.c_void_p, C.c_void_p, _U64, C.c_int, C.c_float, C.c_int, C.c_int, _U64] + [C.POINTER(C.c_void_p)] * 8),
+    ("spmx_nbest_encode_batch_device", C.c_int,
+     [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_int, C.c_void_p, _U64, C.c_void_p, C.c_void_p, C.c_void_p, _U64, C.c_void_p,
+      C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),
+    ("spmx_sample_encode_batch_device", C.c_int,
+     [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_int, C.c_float, _U64, _U64, C.c_void_p, _U64, C.c_void_p, C.c_void_p,
+      C.POINTER(_U64)]),
+    ("spmx_sample_encode_and_score_batch_device", C.c_int,
+     [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_int, C.c_float, C.c_int, C.c_int, _U64, C.c_void_p, _U64, C.c_void_p,
+      C.c_void_p, C.c_void_p, _U64, C.c_void_p, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),
     ("spmx_encode_batch_original", C.c_int, [_H, C.c_void_p, C.c_void_p, _U64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("spmx_split_lines_device", C.c_int,
      [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),

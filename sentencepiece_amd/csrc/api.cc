@@ -82,6 +82,7 @@ struct Ctrl {
   unsigned long long bad_key;         // decode: min over offending (sentence << 32 | id)
   uint32_t big_count[2];              // CompactKernel: document blocks listed for CompactBigKernel (ids; token begins of the spans form)
   uint64_t total_ids;                 // copied from id_offs[n] by the final D2H
+  unsigned long long lattice_max_raw; // LatticeBatchDevice: the longest sentence of the batch (kernels_latticecsr.h latticecsr_maxlen_block)
 };
 
 template <typename T>
@@ -247,6 +248,9 @@ struct Workspace {
   DevBuf<uint32_t> d_tt_len;             // token text (kernels_tokentext.h): item lengths, records, starts; the normalized text's offsets
   DevBuf<uint64_t> d_tt_rec, d_tt_start, d_tt_noffs;
   DevBuf<uint8_t> d_tt_out;              // ... the finished bytes where the caller brings no buffer (the host forms, the file call)
+  DevBuf<uint32_t> d_lc_len;             // lattice results -> CSR (kernels_latticecsr.h): per result its length and its place in
+  DevBuf<unsigned long long> d_lc_src;   // the arena; the two offset arrays where the caller's cannot take them (a capacity query)
+  DevBuf<uint64_t> d_lc_ro, d_lc_io;
   const uint8_t *lit_bytes = nullptr;    // set for the duration of one spmx_decode_batch_pieces call
   const uint32_t *lit_offs = nullptr;
   uint32_t n_lit = 0;
@@ -259,7 +263,7 @@ struct Workspace {
   // against 50 from the fourth on, scripts/host_calls_probe.py)
   uint64_t reserve_text_bytes = 0, reserve_n = 0;
   float bpe_dropout = 0.f;      // set around a call by spmx_sample_encode_batch: BPE-dropout through the long form
-  uint64_t sample_seed = 0;
+  uint64_t sample_seed = 0, sample_index_base = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;          // the general launches run here while the second word round runs on the call's stream
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -275,6 +279,7 @@ struct Workspace {
     d_norm.Free(); d_nbest_scratch.Free(); d_slab.Free(); d_pool.Free(); d_sent_status.Free(); d_flags.Free(); d_res_off.Free();
     d_res_score.Free(); d_dyn_tag.Free(); d_dyn_ent.Free(); d_dyn_list.Free(); d_resume.Free(); d_text.Free(); d_offs.Free(); d_id_offs.Free(); d_ids.Free(); d_dn_text.Free(); d_dn_offs.Free();
     d_tt_len.Free(); d_tt_rec.Free(); d_tt_start.Free(); d_tt_noffs.Free(); d_tt_out.Free();
+    d_lc_len.Free(); d_lc_src.Free(); d_lc_ro.Free(); d_lc_io.Free();
     d_lit_bytes.Free(); d_lit_offs.Free(); d_dec_ids.Free(); d_dec_poffs.Free();
     h_text.Free(); h_offs.Free(); h_id_offs.Free();
     if (d_ctrl) (void)hipFree(d_ctrl);
@@ -1009,7 +1014,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       la.tmp_off = ws->d_tmp_off.p; la.counts = ws->d_counts.p; la.sent_status = d_status; la.status = &ws->d_ctrl->status;
       la.side = &ws->d_ctrl->side; la.arena_tb = spans ? ws->d_arena_tb.p : nullptr;
       la.stack_cap = static_cast<uint32_t>(h->tables.max_piece_len) + 8u;
-      la.dropout = ws->bpe_dropout; la.seed = ws->sample_seed;
+      la.dropout = ws->bpe_dropout; la.seed = ws->sample_seed; la.index_base = ws->sample_index_base;
       la.stats = uni ? &ws->d_ctrl->stats[kStatsPerClass * kSlotLong] : nullptr;
       la.pool_head = &ws->d_ctrl->pool_head;
       uint64_t want = 96ull * text_bytes / (n > count ? n / count : 1) + 4096ull * count + (1ull << 20);
@@ -2661,6 +2666,118 @@ int spmx_encode_batch_spans_device(spmx_handle *h, const void *d_text, uint64_t 
 }
 
 namespace {
+// The front end of every lattice call (kernels_nbest.h), on device text: normalization into the workspace (d_norm, the
+// offsets in d_id_offs), the capacities, the first launch, the wide launches over what it set aside and the arena's regrow.
+// Leaves the results where the kernel writes them -- d_counts (results per sentence), d_res_off / d_span_begin (lengths) /
+// d_res_score per slot [n][K], the id arena d_arena and, for the spans form, d_arena_tb / d_tok_begin -- complete, the
+// stream synchronized, and *used ids in the arena.  max_raw: the longest sentence in raw bytes (the first launch's
+// capacities follow it).  mode and K as LatticeBatchHost documents them.
+int LatticeLaunch(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                  uint64_t max_raw, int mode, uint32_t K, float inv_theta, uint64_t seed, uint64_t index_base, int include_best,
+                  bool spans, hipStream_t st, const char *what, uint64_t *used) {
+  uint64_t ntotal = 0;
+  int rc = GrowOnce(h, ws->d_norm, 2 * text_bytes + 4 * n + 64, &ntotal, 0, [&] {
+    return NormalizeDevice(h, ws, d_text, d_offsets, n, ws->d_norm.p, ws->d_norm.cap, ws->d_id_offs.p, nullptr, st, &ntotal, true);
+  });
+  if (rc != kOk) return rc;
+  if (n * K + 1 > (1ull << 32)) return Fail(h, kInvalidArgument, "too many results for one batch");
+  NBestArgs a{};
+  a.dev = h->dev; a.norm = ws->d_norm.p; a.norm_offs = ws->d_id_offs.p; a.n = static_cast<uint32_t>(n); a.nbest = K;
+  a.mode = static_cast<uint32_t>(mode); a.inv_theta = inv_theta; a.seed = seed; a.index_base = index_base; a.include_best = include_best ? 1u : 0u;
+  const uint64_t hyps0 = static_cast<uint64_t>(K) * 512;   // (a C2 sentence's n-best 5 makes ~1,000; what outgrows the slice runs again)
+  // The first launch's capacities follow the batch: a slice sized for 1024 bytes and 16384 nodes is 0.7 MB a lane, of
+  // which a 126-byte sentence touches a twentieth, and the lanes in flight are what the budget holds (200 k sentences,
+  // n-best 5: 108 ms a call at 697 wavefronts, 94 at 2048).  A sentence that normalizes to more than the guess is set
+  // aside like one beyond the fixed capacities and runs in the wide launch.
+  uint64_t len0 = (max_raw + max_raw / 4 + 16 + 63) & ~static_cast<uint64_t>(63);
+  if (len0 > kNbMaxLen) len0 = kNbMaxLen;
+  uint64_t nodes0 = (len0 + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
+  if (nodes0 > kNbMaxNodes) nodes0 = kNbMaxNodes;
+  const uint64_t hyps_min = h->nbest_hyps_min;
+  // (modes 1 and 4 keep alpha there, len0 + 1 floats of the 2048; mode 3 alpha and H, 2050 floats at 1024 bytes)
+  const uint32_t max_hyps0 = mode == 3 ? static_cast<uint32_t>(len0 / 2 + 2) : (mode != 0 && mode != 5) ? 512u : static_cast<uint32_t>(hyps0 < hyps_min ? hyps_min : (hyps0 > 262144 ? 262144 : hyps0));
+  const uint64_t budget = h->nbest_budget;                  // HBM for the lanes' slices
+  HIP_OR_RETURN(h, ws->d_res_off.Reserve(n * K + 1));
+  HIP_OR_RETURN(h, ws->d_span_begin.Reserve(n * K + 1));     // result lengths
+  HIP_OR_RETURN(h, ws->d_res_score.Reserve(n * K + 1));
+  HIP_OR_RETURN(h, ws->d_counts.Reserve(n + 1));
+  HIP_OR_RETURN(h, ws->d_lists.Reserve(2 * n + 2));          // the sentences beyond a launch's capacities (two lists, in turn)
+  a.res_off = ws->d_res_off.p; a.res_len = ws->d_span_begin.p; a.res_score = ws->d_res_score.p; a.res_count = ws->d_counts.p;
+  a.status = &ws->d_ctrl->status; a.arena_head = &ws->d_ctrl->arena_head;
+  uint64_t arena_need = (ntotal + (4 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * n) * (K < 8 ? K : 8) + 1024;
+  for (int attempt = 0; attempt < 12; ++attempt) {
+    HIP_OR_RETURN(h, ws->d_arena.Reserve(arena_need));
+    a.arena = ws->d_arena.p; a.arena_cap = ws->d_arena.cap;
+    if (spans) {
+      HIP_OR_RETURN(h, ws->d_arena_tb.Reserve(ws->d_arena.cap));
+      HIP_OR_RETURN(h, ws->d_tok_begin.Reserve(ws->d_arena.cap));
+      a.arena_nb = ws->d_arena_tb.p; a.arena_ne = ws->d_tok_begin.p;
+    }
+    HIP_OR_RETURN(h, hipMemsetAsync(ws->d_ctrl, 0, sizeof(Ctrl), st));
+    // first launch: every sentence, 16-bit lattice indices, capacities for the batch (at most kNbMaxLen / kNbMaxNodes)
+    a.max_len = static_cast<uint32_t>(len0); a.max_nodes = static_cast<uint32_t>(nodes0); a.max_hyps = max_hyps0;
+    a.lane_bytes = NbestLaneBytes(a.max_len, a.max_nodes, a.max_hyps, 2);
+    a.list = nullptr; a.n_list = 0;
+    a.retry_list = ws->d_lists.p; a.retry_count = &ws->d_ctrl->retry_count[0]; a.retry_max_len = &ws->d_ctrl->side.over_max_raw;
+    uint64_t waves = (n + 63) / 64;
+    if (waves * 64 * a.lane_bytes > budget) waves = budget / (64 * a.lane_bytes);
+    if (waves > static_cast<uint64_t>(h->n_cu) * 8) waves = static_cast<uint64_t>(h->n_cu) * 8;
+    if (waves < 1) waves = 1;
+    HIP_OR_RETURN(h, ws->d_nbest_scratch.Reserve(waves * 64 * a.lane_bytes));
+    a.scratch = ws->d_nbest_scratch.p;
+    HIP_OR_RETURN(h, LaunchNBest(false, a, static_cast<int>(waves), st));
+    HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_ctrl, ws->d_ctrl, offsetof(Ctrl, total_ids), hipMemcpyDeviceToHost, st));
+    HIP_OR_RETURN(h, hipStreamSynchronize(st));
+    // further launches: 32-bit indices, capacities for the longest sentence set aside; a sentence whose A* needs more
+    // hypotheses than its slice holds is set aside again and the slice grows (the reference's agenda is unbounded too)
+    uint64_t hy_scale = 1;
+    for (int round = 0; ws->h_ctrl->retry_count[round & 1] && !(ws->h_ctrl->status & kStArenaOverflow); ++round) {
+      const uint32_t n_retry = ws->h_ctrl->retry_count[round & 1];
+      // A position starts at most max_prefixes pieces (the deepest chain of pieces that are prefixes of one another)
+      // and one UNK node.
+      const uint64_t L = ws->h_ctrl->side.over_max_raw > kNbMaxLen ? ws->h_ctrl->side.over_max_raw : kNbMaxLen;
+      const uint64_t nodes = (L + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
+      uint64_t hy = mode == 3 ? L / 2 + 512 : (mode != 0 && mode != 5) ? L / 4 + 512 : (static_cast<uint64_t>(K) * (L + 2) * 4 + 16384) * hy_scale;   // modes 1, 4: alpha[L + 1] floats; mode 3: H[L + 1] too
+      if (hy < max_hyps0 * hy_scale) hy = max_hyps0 * hy_scale;
+      if (L >= (1ull << 31) || nodes >= (1ull << 32) || hy >= (1ull << 32)) return Fail(h, kOutOfRange, "a sentence is too long for the lattice");
+      a.max_len = static_cast<uint32_t>(L); a.max_nodes = static_cast<uint32_t>(nodes); a.max_hyps = static_cast<uint32_t>(hy);
+      a.lane_bytes = NbestLaneBytes(a.max_len, a.max_nodes, a.max_hyps, 4);
+      uint64_t lanes = budget / a.lane_bytes;
+      if (lanes < 1) return Fail(h, kResourceExhausted, "out of device memory for the lattice of a sentence of " + std::to_string(L) + " normalized bytes");
+      if (lanes > n_retry) lanes = n_retry;
+      uint64_t w2 = lanes / 64;                           // whole waves within the budget ...
+      const bool partial = w2 == 0;                       // ... or one partial wave: only its first `lanes` lanes own a slice
+      if (partial) w2 = 1;
+      if (w2 > static_cast<uint64_t>(h->n_cu) * 8) w2 = static_cast<uint64_t>(h->n_cu) * 8;
+      a.list = ws->d_lists.p + static_cast<size_t>(round & 1) * n; a.n_list = n_retry;
+      a.retry_list = ws->d_lists.p + static_cast<size_t>((round + 1) & 1) * n;
+      a.retry_count = &ws->d_ctrl->retry_count[(round + 1) & 1];
+      a.retry_max_len = &ws->d_ctrl->side.over_max_raw;
+      HIP_OR_RETURN(h, hipMemsetAsync(a.retry_count, 0, sizeof(uint32_t), st));
+      const uint64_t slices = partial ? lanes : w2 * 64;
+      HIP_OR_RETURN(h, ws->d_nbest_scratch.Reserve(slices * a.lane_bytes));
+      a.scratch = ws->d_nbest_scratch.p;
+      a.live_lanes = static_cast<uint32_t>(slices);
+      HIP_OR_RETURN(h, LaunchNBest(true, a, static_cast<int>(w2), st));
+      a.live_lanes = 0;
+      HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_ctrl, ws->d_ctrl, offsetof(Ctrl, total_ids), hipMemcpyDeviceToHost, st));
+      HIP_OR_RETURN(h, hipStreamSynchronize(st));
+      hy_scale *= 4;
+      if (round == 9 && ws->h_ctrl->retry_count[(round + 1) & 1])
+        return Fail(h, kResourceExhausted, std::string(what) + ": the agenda of a sentence exceeds the device capacities");
+    }
+    const uint32_t stw = ws->h_ctrl->status;
+    if (stw & kStNbestOverflow) return Fail(h, kResourceExhausted, std::string(what) + ": the agenda of a sentence exceeds the device capacities");
+    // (a lane stops at its first result that does not fit, so arena_head is a lower bound: grow geometrically)
+    if (stw & kStArenaOverflow) { arena_need = 4 * ws->d_arena.cap > ws->h_ctrl->arena_head + 1024 ? 4 * ws->d_arena.cap : ws->h_ctrl->arena_head + 1024; continue; }
+    *used = ws->h_ctrl->arena_head;
+    return kOk;
+  }
+  return Fail(h, kInternal, "id arena kept overflowing");
+}
+}  // namespace
+
+namespace {
 // The lattice kernels (kernels_nbest.h), host-buffer form.  mode 0: NBestEncode; 1: Lattice::Sample(inv_theta); 2: the
 // kOriginal encoder (Lattice::Viterbi); 3: Lattice::CalculateEntropy(inv_theta) -- one result without ids per sentence,
 // its score the entropy; 4: SampleEncodeAndScore with replacement -- nbest_size draws per sentence (none for a sentence that
@@ -2729,109 +2846,19 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
     if (text_bytes) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_text.p, text + base, text_bytes, hipMemcpyHostToDevice, st));
     HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     const uint8_t *d_text = ws->d_text.p - base;
-    uint64_t ntotal = 0;
-    int rc = GrowOnce(h, ws->d_norm, 2 * text_bytes + 4 * n + 64, &ntotal, 0, [&] {
-      return NormalizeDevice(h, ws, d_text, ws->d_offs.p, n, ws->d_norm.p, ws->d_norm.cap, ws->d_id_offs.p, nullptr, st, &ntotal, true);
-    });
-    if (rc != kOk) return rc;
-    const uint32_t K = static_cast<uint32_t>(nbest_size);
-    if (n * K + 1 > (1ull << 32)) return Fail(h, kInvalidArgument, "too many results for one batch");
-    NBestArgs a{};
-    a.dev = h->dev; a.norm = ws->d_norm.p; a.norm_offs = ws->d_id_offs.p; a.n = static_cast<uint32_t>(n); a.nbest = K;
-    a.mode = static_cast<uint32_t>(mode); a.inv_theta = inv_theta; a.seed = seed; a.include_best = include_best ? 1u : 0u;
-    const uint64_t hyps0 = static_cast<uint64_t>(K) * 512;   // (a C2 sentence's n-best 5 makes ~1,000; what outgrows the slice runs again)
-    // The first launch's capacities follow the batch: a slice sized for 1024 bytes and 16384 nodes is 0.7 MB a lane, of
-    // which a 126-byte sentence touches a twentieth, and the lanes in flight are what the budget holds (200 k sentences,
-    // n-best 5: 108 ms a call at 697 wavefronts, 94 at 2048).  A sentence that normalizes to more than the guess is set
-    // aside like one beyond the fixed capacities and runs in the wide launch.
     uint64_t max_raw = 0;
     for (uint64_t s = 0; s < n; ++s) max_raw = std::max<uint64_t>(max_raw, offsets[s + 1] - offsets[s]);
-    uint64_t len0 = (max_raw + max_raw / 4 + 16 + 63) & ~static_cast<uint64_t>(63);
-    if (len0 > kNbMaxLen) len0 = kNbMaxLen;
-    uint64_t nodes0 = (len0 + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
-    if (nodes0 > kNbMaxNodes) nodes0 = kNbMaxNodes;
-    const uint64_t hyps_min = h->nbest_hyps_min;
-    // (modes 1 and 4 keep alpha there, len0 + 1 floats of the 2048; mode 3 alpha and H, 2050 floats at 1024 bytes)
-    const uint32_t max_hyps0 = mode == 3 ? static_cast<uint32_t>(len0 / 2 + 2) : (mode != 0 && mode != 5) ? 512u : static_cast<uint32_t>(hyps0 < hyps_min ? hyps_min : (hyps0 > 262144 ? 262144 : hyps0));
-    const uint64_t budget = h->nbest_budget;                  // HBM for the lanes' slices
-    HIP_OR_RETURN(h, ws->d_res_off.Reserve(n * K + 1));
-    HIP_OR_RETURN(h, ws->d_span_begin.Reserve(n * K + 1));     // result lengths
-    HIP_OR_RETURN(h, ws->d_res_score.Reserve(n * K + 1));
-    HIP_OR_RETURN(h, ws->d_counts.Reserve(n + 1));
-    HIP_OR_RETURN(h, ws->d_lists.Reserve(2 * n + 2));          // the sentences beyond a launch's capacities (two lists, in turn)
-    a.res_off = ws->d_res_off.p; a.res_len = ws->d_span_begin.p; a.res_score = ws->d_res_score.p; a.res_count = ws->d_counts.p;
-    a.status = &ws->d_ctrl->status; a.arena_head = &ws->d_ctrl->arena_head;
-    uint64_t arena_need = (ntotal + (4 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * n) * (K < 8 ? K : 8) + 1024;
-    for (int attempt = 0; attempt < 12; ++attempt) {
-      HIP_OR_RETURN(h, ws->d_arena.Reserve(arena_need));
-      a.arena = ws->d_arena.p; a.arena_cap = ws->d_arena.cap;
-      if (spans) {
-        HIP_OR_RETURN(h, ws->d_arena_tb.Reserve(ws->d_arena.cap));
-        HIP_OR_RETURN(h, ws->d_tok_begin.Reserve(ws->d_arena.cap));
-        a.arena_nb = ws->d_arena_tb.p; a.arena_ne = ws->d_tok_begin.p;
-      }
-      HIP_OR_RETURN(h, hipMemsetAsync(ws->d_ctrl, 0, sizeof(Ctrl), st));
-      // first launch: every sentence, 16-bit lattice indices, capacities for the batch (at most kNbMaxLen / kNbMaxNodes)
-      a.max_len = static_cast<uint32_t>(len0); a.max_nodes = static_cast<uint32_t>(nodes0); a.max_hyps = max_hyps0;
-      a.lane_bytes = NbestLaneBytes(a.max_len, a.max_nodes, a.max_hyps, 2);
-      a.list = nullptr; a.n_list = 0;
-      a.retry_list = ws->d_lists.p; a.retry_count = &ws->d_ctrl->retry_count[0]; a.retry_max_len = &ws->d_ctrl->side.over_max_raw;
-      uint64_t waves = (n + 63) / 64;
-      if (waves * 64 * a.lane_bytes > budget) waves = budget / (64 * a.lane_bytes);
-      if (waves > static_cast<uint64_t>(h->n_cu) * 8) waves = static_cast<uint64_t>(h->n_cu) * 8;
-      if (waves < 1) waves = 1;
-      HIP_OR_RETURN(h, ws->d_nbest_scratch.Reserve(waves * 64 * a.lane_bytes));
-      a.scratch = ws->d_nbest_scratch.p;
-      HIP_OR_RETURN(h, LaunchNBest(false, a, static_cast<int>(waves), st));
-      HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_ctrl, ws->d_ctrl, offsetof(Ctrl, total_ids), hipMemcpyDeviceToHost, st));
-      HIP_OR_RETURN(h, hipStreamSynchronize(st));
-      // further launches: 32-bit indices, capacities for the longest sentence set aside; a sentence whose A* needs more
-      // hypotheses than its slice holds is set aside again and the slice grows (the reference's agenda is unbounded too)
-      uint64_t hy_scale = 1;
-      for (int round = 0; ws->h_ctrl->retry_count[round & 1] && !(ws->h_ctrl->status & kStArenaOverflow); ++round) {
-        const uint32_t n_retry = ws->h_ctrl->retry_count[round & 1];
-        // A position starts at most max_prefixes pieces (the deepest chain of pieces that are prefixes of one another)
-        // and one UNK node.
-        const uint64_t L = ws->h_ctrl->side.over_max_raw > kNbMaxLen ? ws->h_ctrl->side.over_max_raw : kNbMaxLen;
-        const uint64_t nodes = (L + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
-        uint64_t hy = mode == 3 ? L / 2 + 512 : (mode != 0 && mode != 5) ? L / 4 + 512 : (static_cast<uint64_t>(K) * (L + 2) * 4 + 16384) * hy_scale;   // modes 1, 4: alpha[L + 1] floats; mode 3: H[L + 1] too
-        if (hy < max_hyps0 * hy_scale) hy = max_hyps0 * hy_scale;
-        if (L >= (1ull << 31) || nodes >= (1ull << 32) || hy >= (1ull << 32)) return Fail(h, kOutOfRange, "a sentence is too long for the lattice");
-        a.max_len = static_cast<uint32_t>(L); a.max_nodes = static_cast<uint32_t>(nodes); a.max_hyps = static_cast<uint32_t>(hy);
-        a.lane_bytes = NbestLaneBytes(a.max_len, a.max_nodes, a.max_hyps, 4);
-        uint64_t lanes = budget / a.lane_bytes;
-        if (lanes < 1) return Fail(h, kResourceExhausted, "out of device memory for the lattice of a sentence of " + std::to_string(L) + " normalized bytes");
-        if (lanes > n_retry) lanes = n_retry;
-        uint64_t w2 = lanes / 64;                           // whole waves within the budget ...
-        const bool partial = w2 == 0;                       // ... or one partial wave: only its first `lanes` lanes own a slice
-        if (partial) w2 = 1;
-        if (w2 > static_cast<uint64_t>(h->n_cu) * 8) w2 = static_cast<uint64_t>(h->n_cu) * 8;
-        a.list = ws->d_lists.p + static_cast<size_t>(round & 1) * n; a.n_list = n_retry;
-        a.retry_list = ws->d_lists.p + static_cast<size_t>((round + 1) & 1) * n;
-        a.retry_count = &ws->d_ctrl->retry_count[(round + 1) & 1];
-        a.retry_max_len = &ws->d_ctrl->side.over_max_raw;
-        HIP_OR_RETURN(h, hipMemsetAsync(a.retry_count, 0, sizeof(uint32_t), st));
-        const uint64_t slices = partial ? lanes : w2 * 64;
-        HIP_OR_RETURN(h, ws->d_nbest_scratch.Reserve(slices * a.lane_bytes));
-        a.scratch = ws->d_nbest_scratch.p;
-        a.live_lanes = static_cast<uint32_t>(slices);
-        HIP_OR_RETURN(h, LaunchNBest(true, a, static_cast<int>(w2), st));
-        a.live_lanes = 0;
-        HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_ctrl, ws->d_ctrl, offsetof(Ctrl, total_ids), hipMemcpyDeviceToHost, st));
-        HIP_OR_RETURN(h, hipStreamSynchronize(st));
-        hy_scale *= 4;
-        if (round == 9 && ws->h_ctrl->retry_count[(round + 1) & 1])
-          return Fail(h, kResourceExhausted, std::string(what) + ": the agenda of a sentence exceeds the device capacities");
-      }
-      const uint32_t stw = ws->h_ctrl->status;
-      if (stw & kStNbestOverflow) return Fail(h, kResourceExhausted, std::string(what) + ": the agenda of a sentence exceeds the device capacities");
-      // (a lane stops at its first result that does not fit, so arena_head is a lower bound: grow geometrically)
-      if (stw & kStArenaOverflow) { arena_need = 4 * ws->d_arena.cap > ws->h_ctrl->arena_head + 1024 ? 4 * ws->d_arena.cap : ws->h_ctrl->arena_head + 1024; continue; }
+    const uint32_t K = static_cast<uint32_t>(nbest_size);
+    uint64_t used = 0;
+    if (int rc = LatticeLaunch(h, ws, d_text, text_bytes, ws->d_offs.p, n, max_raw, mode, K, inv_theta, seed, 0, include_best, spans, st,
+                               what, &used);
+        rc != kOk)
+      return rc;
+    {
       // results -> host CSR.  The result arrays land in ONE pinned staging block (the workspace's h_text, idle in this
       // call) by asynchronous copies behind one synchronisation -- copies into fresh pageable vectors and a single-thread
       // assembly were 100 of a 178 ms call of 200 k sentences x 5 results beside 76 ms of kernel -- and the CSR is put
       // together by a few threads over ranges of sentences (where a sentence's results go follows from a prefix pass).
-      const uint64_t used = ws->h_ctrl->arena_head;
       auto al16 = [](uint64_t x) { return (x + 15u) & ~static_cast<uint64_t>(15); };
       const uint64_t b_cnt = 0, b_len = b_cnt + al16(n * 4), b_off = b_len + al16(n * K * 4), b_sc = b_off + al16(n * K * 8),
                      b_ar = b_sc + al16(n * K * 4), b_nb = b_ar + al16(used * 4), b_ne = b_nb + (spans ? al16(used * 4) : 0),
@@ -2965,7 +2992,6 @@ int LatticeBatchHost(spmx_handle *h, const char *text, const uint64_t *offsets, 
       if (spans) { *begin = sb; *end = se; *nbegin = snb; *nend = sne; }
       return kOk;
     }
-    return Fail(h, kInternal, "id arena kept overflowing");
   }
 }
 }  // namespace
@@ -3174,6 +3200,246 @@ int SampleEncodeImpl(spmx_handle *h, const char *text, const uint64_t *offsets, 
   });
 }
 }  // namespace
+
+/* ---- the lattice calls on device buffers (kernels_latticecsr.h) -------------------------------------------------------
+ * LatticeLaunch as the host forms run it, then the results go from the kernel's sparse arena to the caller's dense CSR on
+ * the device: no copy of the arena to the host, no host assembly, no host draw. */
+namespace {
+struct LatticeOut {                  // the caller's device buffers
+  int32_t *ids; uint64_t ids_capacity;
+  uint64_t *id_offsets;              // results_capacity + 1
+  float *scores;                     // results_capacity, null: not asked for
+  uint32_t *sent_of_result;          // results_capacity, null: not asked for
+  uint64_t results_capacity;
+  uint64_t *result_offsets;          // n + 1, null: not asked for
+  int32_t *nbegin = nullptr, *nend = nullptr;   // ids_capacity each, both or none: per id its token's range of the normalized
+                                     // sentence in DEVICE form (U+2581 one byte), the negative bos / eos markers as the kernel
+                                     // writes them (lattice branches only)
+};
+
+// The branches that are the plain encoder (or BPE-dropout, set up by the caller in the workspace): one result per
+// sentence, score 0.
+int PlainResultsDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                       const LatticeOut &o, hipStream_t stream, uint64_t *total_results, uint64_t *total_ids) {
+  *total_results = n;
+  if (n == 0) {
+    if (o.id_offsets) HIP_OR_RETURN(h, hipMemsetAsync(o.id_offsets, 0, sizeof(uint64_t), stream));
+    if (o.result_offsets) HIP_OR_RETURN(h, hipMemsetAsync(o.result_offsets, 0, sizeof(uint64_t), stream));
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+    return kOk;
+  }
+  const bool rows_fit = o.id_offsets && o.results_capacity >= n;
+  if (!rows_fit) HIP_OR_RETURN(h, ws->d_lc_io.Reserve(n + 1));
+  if (int rc = EncodeDevice(h, ws, d_text, text_bytes, d_offsets, n, rows_fit ? o.ids : nullptr, rows_fit ? o.ids_capacity : 0,
+                            rows_fit ? o.id_offsets : ws->d_lc_io.p, nullptr, stream, total_ids, nullptr);
+      rc != kOk)
+    return rc;
+  if (!rows_fit) return Fail(h, kResourceExhausted, "results_capacity is too small");
+  if (o.result_offsets || o.sent_of_result || o.scores) {
+    LatticeIotaArgs ia{n, o.result_offsets, o.sent_of_result, o.scores};
+    const uint64_t blocks = (n + 1 + 63) / 64, wide = static_cast<uint64_t>(h->n_cu) * 16;
+    HIP_OR_RETURN(h, LaunchLatticeIota(ia, static_cast<int>(blocks < wide ? blocks : wide), stream));
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  }
+  return kOk;
+}
+
+// one_each: every sentence owns exactly one result (Lattice::Sample, or the row the pick kernel chose out of K): the rows
+// are the sentences and no result_offsets are made.  pick: draw that row first, with probability ~ exp(pick_alpha * score).
+int LatticeBatchDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                       int mode, uint32_t K, float inv_theta, uint64_t seed, uint64_t index_base, int include_best, bool one_each,
+                       bool pick, float pick_alpha, const char *what, const LatticeOut &o, hipStream_t stream, uint64_t *total_results,
+                       uint64_t *total_ids) {
+  if (n >= (1ull << 32) - 64) return Fail(h, kInvalidArgument, "more than 2^32 - 64 sentences in one batch");
+  // the first launch's capacities follow the longest sentence: a max-reduction over the offsets, one word to the host
+  const uint64_t wide = static_cast<uint64_t>(h->n_cu) * 16;
+  auto grid_of = [&](uint64_t units) { return static_cast<int>(units < 1 ? 1 : (units < wide ? units : wide)); };
+  unsigned long long max_raw = 0;
+  {
+    unsigned long long *d_max = &ws->d_ctrl->lattice_max_raw;
+    HIP_OR_RETURN(h, hipMemsetAsync(d_max, 0, sizeof(*d_max), stream));
+    LatticeMaxLenArgs ma{d_offsets, n, d_max};
+    HIP_OR_RETURN(h, LaunchLatticeMaxLen(ma, grid_of((n + 63) / 64), stream));
+    HIP_OR_RETURN(h, hipMemcpyAsync(&max_raw, d_max, sizeof(max_raw), hipMemcpyDeviceToHost, stream));
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  }
+  HIP_OR_RETURN(h, ws->d_id_offs.Reserve(n + 1));
+  uint64_t used = 0;
+  const bool spans = o.nbegin != nullptr && o.nend != nullptr;
+  if (int rc = LatticeLaunch(h, ws, d_text, text_bytes, d_offsets, n, max_raw, mode, K, inv_theta, seed, index_base, include_best, spans,
+                             stream, what, &used);
+      rc != kOk)
+    return rc;
+  auto scan = [&](const uint32_t *counts, uint64_t count, uint64_t *offs) -> int {
+    HIP_OR_RETURN(h, ws->d_tile_sums.Reserve((count + kScanTile - 1) / kScanTile + 2));
+    ScanArgs sa{counts, static_cast<uint32_t>(count), ws->d_tile_sums.p, offs};
+    const uint32_t tiles = (static_cast<uint32_t>(count) + kScanTile - 1) / kScanTile;
+    HIP_OR_RETURN(h, LaunchScan(sa, static_cast<int>(tiles < static_cast<uint32_t>(h->n_cu * 8) ? tiles : h->n_cu * 8), stream));
+    return kOk;
+  };
+  if (pick) {
+    LatticePickArgs pa{ws->d_counts.p, ws->d_res_off.p, ws->d_span_begin.p, ws->d_res_score.p, K, n, pick_alpha, seed, index_base};
+    HIP_OR_RETURN(h, LaunchLatticePick(pa, grid_of((n + 63) / 64), stream));
+  }
+  uint64_t R = n;
+  const uint64_t *ro = nullptr;
+  if (!one_each) {
+    uint64_t *w = o.result_offsets;
+    if (!w) { HIP_OR_RETURN(h, ws->d_lc_ro.Reserve(n + 1)); w = ws->d_lc_ro.p; }
+    if (int rc = scan(ws->d_counts.p, n, w); rc != kOk) return rc;
+    HIP_OR_RETURN(h, hipMemcpyAsync(&R, w + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+    ro = w;
+  }
+  *total_results = R;
+  if (R >= (1ull << 32) - 64) return Fail(h, kInvalidArgument, "more than 2^32 - 64 results in one batch");
+  const bool rows_fit = o.id_offsets && R <= o.results_capacity;
+  uint64_t *io = o.id_offsets;
+  if (!rows_fit) { HIP_OR_RETURN(h, ws->d_lc_io.Reserve(R + 1)); io = ws->d_lc_io.p; }
+  LatticeCsrArgs c{};
+  c.res_off = ws->d_res_off.p; c.res_len = ws->d_span_begin.p; c.res_score = ws->d_res_score.p; c.K = K; c.n = n;
+  c.result_offs = ro; c.R = R;
+  uint64_t T = 0;
+  if (R) {
+    HIP_OR_RETURN(h, ws->d_lc_len.Reserve(R));
+    HIP_OR_RETURN(h, ws->d_lc_src.Reserve(R));
+    c.row_len = ws->d_lc_len.p; c.row_src = ws->d_lc_src.p;
+    c.scores = rows_fit ? o.scores : nullptr; c.sent_of_result = rows_fit ? o.sent_of_result : nullptr;
+    HIP_OR_RETURN(h, LaunchLatticeCsr(false, c, grid_of((R + kLcRowChunk - 1) / kLcRowChunk), stream));
+    if (int rc = scan(ws->d_lc_len.p, R, io); rc != kOk) return rc;
+    HIP_OR_RETURN(h, hipMemcpyAsync(&T, io + R, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  } else {
+    HIP_OR_RETURN(h, hipMemsetAsync(io, 0, sizeof(uint64_t), stream));
+  }
+  HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  *total_ids = T;
+  if (!rows_fit) return Fail(h, kResourceExhausted, "results_capacity is too small");
+  if (T > o.ids_capacity || (T && !o.ids)) return Fail(h, kResourceExhausted, "ids_capacity is too small");
+  if (T) {
+    c.id_offs = io; c.arena = ws->d_arena.p; c.out = o.ids; c.T = T;
+    HIP_OR_RETURN(h, LaunchLatticeCsr(true, c, grid_of((T + 3 + kLcOutChunk - 1) / kLcOutChunk), stream));
+    if (spans) {                                            // the span arenas are indexed like the id arena
+      c.arena = ws->d_arena_tb.p; c.out = o.nbegin;
+      HIP_OR_RETURN(h, LaunchLatticeCsr(true, c, grid_of((T + 3 + kLcOutChunk - 1) / kLcOutChunk), stream));
+      c.arena = ws->d_tok_begin.p; c.out = o.nend;
+      HIP_OR_RETURN(h, LaunchLatticeCsr(true, c, grid_of((T + 3 + kLcOutChunk - 1) / kLcOutChunk), stream));
+    }
+    HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  }
+  return kOk;
+}
+}  // namespace
+
+namespace {
+// NBestEncode into the caller's device buffers, on a leased workspace; nbest_size within [1, 1024], a unigram model
+int NBestDeviceWs(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                  int nbest_size, const LatticeOut &o, hipStream_t stream, uint64_t *total_results, uint64_t *total_ids) {
+  if (n == 0 || nbest_size == 1)                            // :694-696 the plain encoder, score 0.0
+    return PlainResultsDevice(h, ws, d_text, text_bytes, d_offsets, n, o, stream, total_results, total_ids);
+  return LatticeBatchDevice(h, ws, d_text, text_bytes, d_offsets, n, 0, static_cast<uint32_t>(nbest_size), 0.f, 0, 0, 0, false, false, 0.f,
+                            "NBestEncode", o, stream, total_results, total_ids);
+}
+
+// the refusals of SampleEncode that do not depend on the batch (src/sentencepiece_processor.cc:684-691)
+int SampleRefusal(spmx_handle *h, int nbest_size) {
+  if (nbest_size > 512) return Fail(h, kInternal, "nbest_size must be nbest_size <= 512");   // :684
+  if (h->model.model_type == kWord || h->model.model_type == kChar)
+    return Fail(h, kInternal, "SampleEncode is not available for the current model.");   // :689-691
+  return kOk;
+}
+
+// SampleEncode into the caller's device buffers, on a leased workspace, behind SampleRefusal: every branch of SampleEncodeImpl
+int SampleDeviceWs(spmx_handle *h, Workspace *ws, const uint8_t *text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                   int nbest_size, float alpha, uint64_t seed, uint64_t index_base, int32_t *d_ids, uint64_t ids_capacity,
+                   uint64_t *d_id_offsets, hipStream_t stream, uint64_t *total_ids, uint32_t *d_sent = nullptr, int32_t *d_nbegin = nullptr,
+                   int32_t *d_nend = nullptr) {
+  const LatticeOut o{d_ids, ids_capacity, d_id_offsets, nullptr, d_sent, n, nullptr, d_nbegin, d_nend};
+  uint64_t results = 0;
+  if (h->model.model_type == kBpe) {                        // every nbest_size is BPE-dropout (:688-693); alpha <= 0: the plain merge order
+    if (n && alpha > 0.f) { ws->bpe_dropout = alpha; ws->sample_seed = seed; ws->sample_index_base = index_base; }
+    struct Reset { Workspace *w; ~Reset() { w->bpe_dropout = 0.f; w->sample_seed = 0; w->sample_index_base = 0; } } reset{ws};
+    return PlainResultsDevice(h, ws, text, text_bytes, d_offsets, n, o, stream, &results, total_ids);
+  }
+  if (n == 0 || nbest_size == 0 || nbest_size == 1)
+    return PlainResultsDevice(h, ws, text, text_bytes, d_offsets, n, o, stream, &results, total_ids);
+  if (nbest_size < 0)                                       // Lattice::Sample(alpha): one result per sentence
+    return LatticeBatchDevice(h, ws, text, text_bytes, d_offsets, n, 1, 1, alpha, seed, index_base, 0, true, false, 0.f, "SampleEncode", o,
+                              stream, &results, total_ids);
+  // one of the nbest_size best: the search of NBestEncode (mode 0 draws nothing), then the pick, keyed by (seed, index_base + s)
+  return LatticeBatchDevice(h, ws, text, text_bytes, d_offsets, n, 0, static_cast<uint32_t>(nbest_size), 0.f, seed, index_base, 0, true, true,
+                            alpha, "SampleEncode", o, stream, &results, total_ids);
+}
+}  // namespace
+
+int spmx_nbest_encode_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                                   int nbest_size, int32_t *d_ids, uint64_t ids_capacity, uint64_t *d_id_offsets, float *d_scores,
+                                   uint32_t *d_sent_of_result, uint64_t results_capacity, uint64_t *d_result_offsets, void *stream_v,
+                                   uint64_t *total_results, uint64_t *total_ids) {
+  if (!h) return kInvalidArgument;
+  if (!total_results || !total_ids) return Fail(h, kInternal, "output container is null");
+  *total_results = 0;
+  *total_ids = 0;
+  return Guard(h, [&]() -> int {
+    if (h->model.model_type != kUnigram) return Fail(h, kInternal, "NBestEncode is not available for the current model.");   // sentencepiece_processor.cc:662
+    if (n && !d_offsets) return Fail(h, kInvalidArgument, "null offsets");
+    if (d_id_offsets && results_capacity && !d_scores) return Fail(h, kInvalidArgument, "null scores");
+    if (nbest_size > 1024) nbest_size = 1024;                                              // unigram_model.cc:692
+    if (nbest_size < 1) nbest_size = 1;
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const LatticeOut o{d_ids, ids_capacity, d_id_offsets, d_scores, d_sent_of_result, results_capacity, d_result_offsets};
+    return NBestDeviceWs(h, L.ws.get(), static_cast<const uint8_t *>(d_text), text_bytes, d_offsets, n, nbest_size, o, stream, total_results,
+                         total_ids);
+  });
+}
+
+int spmx_sample_encode_and_score_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets,
+                                              uint64_t n, int num_samples, float alpha, int wor, int include_best, uint64_t seed,
+                                              int32_t *d_ids, uint64_t ids_capacity, uint64_t *d_id_offsets, float *d_scores,
+                                              uint32_t *d_sent_of_result, uint64_t results_capacity, uint64_t *d_result_offsets,
+                                              void *stream_v, uint64_t *total_results, uint64_t *total_ids) {
+  if (!h) return kInvalidArgument;
+  if (!total_results || !total_ids) return Fail(h, kInternal, "output container is null");
+  *total_results = 0;
+  *total_ids = 0;
+  return Guard(h, [&]() -> int {
+    if (h->model.model_type != kUnigram)
+      return Fail(h, kInternal, "SampleEncodeAndScore is not available for the current model.");   // :727-728
+    if ((include_best && !wor) || num_samples < 1) return Fail(h, kInternal, "SampleEncodeAndScore returns empty result.");
+    if (num_samples > 512) return Fail(h, kInternal, "num_samples must be num_samples <= 512");
+    if (n && !d_offsets) return Fail(h, kInvalidArgument, "null offsets");
+    if (d_id_offsets && results_capacity && !d_scores) return Fail(h, kInvalidArgument, "null scores");
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const LatticeOut o{d_ids, ids_capacity, d_id_offsets, d_scores, d_sent_of_result, results_capacity, d_result_offsets};
+    if (n == 0)
+      return PlainResultsDevice(h, L.ws.get(), static_cast<const uint8_t *>(d_text), text_bytes, d_offsets, n, o, stream, total_results, total_ids);
+    return LatticeBatchDevice(h, L.ws.get(), static_cast<const uint8_t *>(d_text), text_bytes, d_offsets, n, wor ? 5 : 4,
+                              static_cast<uint32_t>(wor ? num_samples + 2 : num_samples), alpha, seed, 0, include_best, false, false, 0.f,
+                              "SampleEncodeAndScore", o, stream, total_results, total_ids);
+  });
+}
+
+int spmx_sample_encode_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                                    int nbest_size, float alpha, uint64_t seed, uint64_t index_base, int32_t *d_ids,
+                                    uint64_t ids_capacity, uint64_t *d_id_offsets, void *stream_v, uint64_t *total_ids) {
+  if (!h) return kInvalidArgument;
+  if (!total_ids) return Fail(h, kInternal, "output container is null");
+  *total_ids = 0;
+  return Guard(h, [&]() -> int {
+    if (int rc = SampleRefusal(h, nbest_size); rc != kOk) return rc;
+    if (n && !d_offsets) return Fail(h, kInvalidArgument, "null offsets");
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    return SampleDeviceWs(h, L.ws.get(), static_cast<const uint8_t *>(d_text), text_bytes, d_offsets, n, nbest_size, alpha, seed, index_base,
+                          d_ids, ids_capacity, d_id_offsets, static_cast<hipStream_t>(stream_v), total_ids);
+  });
+}
 
 int spmx_normalize_batch_device(spmx_handle *h, const void *d_text, const uint64_t *d_offsets, uint64_t n, void *d_norm,
                                 uint64_t norm_capacity, uint64_t *d_norm_offsets, uint32_t *d_norm_to_orig, void *stream,
@@ -3772,7 +4038,8 @@ struct TextChunk {
   ScratchBuf<uint8_t> d_file;
   uint64_t n_lines = 0, total = 0, image = 0;
 };
-int EncodeChunk(spmx_handle *h, TextChunk &c, const uint8_t *src, uint64_t bytes, bool piece) {
+// chunk -> the workspace's d_text / d_offs (c.n_lines sentences, *text_bytes bytes)
+int StageChunk(spmx_handle *h, TextChunk &c, const uint8_t *src, uint64_t bytes, uint64_t *text_bytes_out) {
   Workspace *ws = c.ws;
   hipStream_t st = ws->stream;
   uint64_t nl = 0;
@@ -3792,8 +4059,15 @@ int EncodeChunk(spmx_handle *h, TextChunk &c, const uint8_t *src, uint64_t bytes
   HIP_OR_RETURN(h, hipMemcpyAsync(c.d_file.p, ws->h_text.p, bytes, hipMemcpyHostToDevice, st));
   uint64_t text_bytes = 0;
   c.n_lines = c.total = c.image = 0;
-  int r = spmx_split_lines_device(h, c.d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &c.n_lines, &text_bytes);
-  if (r != kOk) return r;
+  const int r = spmx_split_lines_device(h, c.d_file.p, bytes, ws->d_text.p, ws->d_text.cap, ws->d_offs.p, ws->d_offs.cap, st, &c.n_lines, &text_bytes);
+  *text_bytes_out = text_bytes;
+  return r;
+}
+int EncodeChunk(spmx_handle *h, TextChunk &c, const uint8_t *src, uint64_t bytes, bool piece) {
+  Workspace *ws = c.ws;
+  hipStream_t st = ws->stream;
+  uint64_t text_bytes = 0;
+  if (int r = StageChunk(h, c, src, bytes, &text_bytes); r != kOk) return r;
   if (piece) return PieceLines(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, c.n_lines, nullptr, 0, true, st, &c.total, &c.image);
   return EncodeIntoArena(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, c.n_lines, st, &c.total, nullptr);
 }
@@ -3889,6 +4163,182 @@ int spmx_encode_file(spmx_handle *h, const char *in_path, const char *out_path, 
     if (int rc = RunChunks<Scratch>(h, cut.size() - 1, true, process, commit); rc != kOk) return rc;
     if (bin) fwrite(&id_total, sizeof(uint64_t), 1, idx.f);      // the closing offset
     if (n_sentences) *n_sentences = sent_total;
+    if (n_ids) *n_ids = id_total;
+    return kOk;
+  });
+}
+
+/* ---- corpus file -> the lattice formats of spm_encode (src/spm_encode_main.cc:120-153) ------------------------------------
+ * nbest_id: NBestEncode per line, one output line per result; sample_id: SampleEncode per line, one output line.  The chunk
+ * pipeline of spmx_encode_file with, per chunk, StageChunk -> the lattice call's device form into the worker's own buffers
+ * (grown once to the reported needs) -> the id-line writer over the RESULT CSR, which is the lines CSR -> one D2H of the
+ * image.  A sample chunk passes its first global line number as index_base: the draws depend on (seed, line number) alone. */
+int spmx_encode_file_ex(spmx_handle *h, const char *in_path, const char *out_path, const char *format, int nbest_size, float alpha,
+                        uint64_t seed, uint64_t *n_sentences, uint64_t *n_lines, uint64_t *n_ids) {
+  if (!h) return kInvalidArgument;
+  if (n_sentences) *n_sentences = 0;
+  if (n_lines) *n_lines = 0;
+  if (n_ids) *n_ids = 0;
+  const std::string fmt = format ? format : "id";
+  if (fmt == "id" || fmt == "piece" || fmt == "bin") {
+    uint64_t ns = 0;
+    const int rc = spmx_encode_file(h, in_path, out_path, fmt.c_str(), &ns, n_ids);
+    if (n_sentences) *n_sentences = ns;
+    if (n_lines) *n_lines = ns;
+    return rc;
+  }
+  return Guard(h, [&]() -> int {
+    const std::string out_name = out_path ? out_path : "";
+    if (fmt == "proto" || fmt == "sample_proto" || fmt == "nbest_proto") {      // :120-121, :132-135, :150-153 write nothing
+      OutFile out;
+      if (!out.Open(out_name)) return Fail(h, kPermissionDenied, "cannot write \"" + out_name + "\"");
+      return kOk;
+    }
+    const bool nbest = fmt == "nbest_id" || fmt == "nbest_piece", piece = fmt == "nbest_piece" || fmt == "sample_piece";
+    if (!nbest && fmt != "sample_id" && fmt != "sample_piece")
+      return Fail(h, kInvalidArgument, "format must be \"id\", \"piece\", \"bin\", \"nbest_id\", \"nbest_piece\", \"sample_id\", \"sample_piece\" or one of the proto formats");
+    int k = nbest_size;
+    if (nbest) {
+      if (h->model.model_type != kUnigram) return Fail(h, kInternal, "NBestEncode is not available for the current model.");   // sentencepiece_processor.cc:662
+      if (k > 1024) k = 1024;                                                              // unigram_model.cc:692
+      if (k < 1) k = 1;
+    } else if (int rc = SampleRefusal(h, k); rc != kOk) {
+      return rc;
+    }
+    MappedFile file;
+    if (int r = file.Open(h, in_path ? in_path : ""); r != kOk) return r;
+    OutFile out;
+    if (!out.Open(out_name)) return Fail(h, kPermissionDenied, "cannot write \"" + out_name + "\"");
+    const std::vector<uint64_t> cut = CutAtLineEnds(file.p, file.size, FileChunkTarget());
+    // the global number of every chunk's first line (getline: a last line without '\n' counts)
+    std::vector<uint64_t> line_base(cut.size(), 0);
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+      uint64_t nl = 0;
+      const uint8_t *p = file.p + cut[c], *e = file.p + cut[c + 1];
+      while (p < e) {
+        const void *q = memchr(p, '\n', static_cast<size_t>(e - p));
+        if (!q) { ++nl; break; }
+        ++nl;
+        p = static_cast<const uint8_t *>(q) + 1;
+      }
+      line_base[c + 1] = line_base[c] + nl;
+    }
+    uint64_t sent_total = 0, line_total = 0, id_total = 0;
+    struct Scratch : TextChunk {
+      ScratchBuf<int32_t> d_ids;
+      ScratchBuf<uint64_t> d_io, d_ro;
+      ScratchBuf<float> d_sc;
+      // the piece formats: dense token ranges, the results' sentences and normalized bases, the reference-form normalized
+      // text (16 bytes of slack) and its offsets, the stand-in flags and their prefix sums
+      ScratchBuf<int32_t> d_nb, d_ne;
+      ScratchBuf<uint32_t> d_sent, d_flag;
+      ScratchBuf<uint8_t> d_rnorm;
+      ScratchBuf<uint64_t> d_rnoffs, d_pre, d_rbase;
+      uint64_t results = 0;
+    };
+    // the branches that are the plain encoder or BPE-dropout: one result per line, the existing piece-line path
+    const bool plain = nbest ? k == 1 : (h->model.model_type == kBpe || k == 0 || k == 1);
+    auto process = [&](Scratch &s, uint64_t c) -> int {
+      Workspace *ws = s.ws;
+      hipStream_t st = ws->stream;
+      uint64_t text_bytes = 0;
+      if (int r = StageChunk(h, s, file.p + cut[c], cut[c + 1] - cut[c], &text_bytes); r != kOk) return r;
+      const uint64_t n = s.n_lines;
+      if (n != line_base[c + 1] - line_base[c]) return Fail(h, kInternal, "the line splitter and the host disagree about a chunk's lines");
+      if (piece && plain) {
+        if (!nbest && h->model.model_type == kBpe && alpha > 0.f) { ws->bpe_dropout = alpha; ws->sample_seed = seed; ws->sample_index_base = line_base[c]; }
+        struct Reset { Workspace *w; ~Reset() { w->bpe_dropout = 0.f; w->sample_seed = 0; w->sample_index_base = 0; } } reset{ws};
+        s.results = n; s.total = s.image = 0;
+        if (int r = PieceLines(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n, nullptr, 0, true, st, &s.total, &s.image); r != kOk) return r;
+        HIP_OR_RETURN(h, ws->h_text.Reserve(s.image + 32));
+        if (s.image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, ws->d_tt_out.p, s.image, hipMemcpyDeviceToHost, st));
+        HIP_OR_RETURN(h, hipStreamSynchronize(st));
+        return kOk;
+      }
+      if (piece) {                                                  // the reference-form normalized text, before the lattice call takes the workspace
+        HIP_OR_RETURN(h, s.d_rnoffs.Reserve(n + 1));
+        uint64_t rtotal = 0;
+        const int r = GrowOnce(h, s.d_rnorm, 2 * text_bytes + 4 * n + 64 + 16, &rtotal, 16, [&] {
+          return NormalizeDevice(h, ws, ws->d_text.p, ws->d_offs.p, n, s.d_rnorm.p, s.d_rnorm.cap - 16, s.d_rnoffs.p, nullptr, st, &rtotal);
+        });
+        if (r != kOk) return r;
+      }
+      HIP_OR_RETURN(h, s.d_ro.Reserve(n + 1));
+      uint64_t R = nbest ? n * static_cast<uint64_t>(k < 8 ? k : 8) : n, T = IdsGuess(h, text_bytes, n) * static_cast<uint64_t>(nbest ? (k < 8 ? k : 8) : 1);
+      int rc = kOk;
+      for (int attempt = 0; attempt < 2; ++attempt) {                 // the capacity protocol, one retry at the reported needs
+        HIP_OR_RETURN(h, s.d_ids.Reserve(T + 1));
+        HIP_OR_RETURN(h, s.d_io.Reserve(R + 1));
+        if (nbest) HIP_OR_RETURN(h, s.d_sc.Reserve(R + 1));
+        if (piece) {
+          HIP_OR_RETURN(h, s.d_nb.Reserve(T + 1));
+          HIP_OR_RETURN(h, s.d_ne.Reserve(T + 1));
+          HIP_OR_RETURN(h, s.d_sent.Reserve(R + 1));
+        }
+        uint64_t icap = s.d_ids.cap, rcap = s.d_io.cap - 1;
+        if (nbest) rcap = std::min<uint64_t>(rcap, s.d_sc.cap);
+        if (piece) { icap = std::min<uint64_t>(icap, std::min<uint64_t>(s.d_nb.cap, s.d_ne.cap)); rcap = std::min<uint64_t>(rcap, s.d_sent.cap); }
+        uint64_t tr = n, ti = 0;
+        if (nbest) {
+          const LatticeOut o{s.d_ids.p, icap, s.d_io.p, s.d_sc.p, piece ? s.d_sent.p : nullptr, rcap, s.d_ro.p, piece ? s.d_nb.p : nullptr,
+                             piece ? s.d_ne.p : nullptr};
+          rc = NBestDeviceWs(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n, k, o, st, &tr, &ti);
+        } else {
+          if (rcap < n) { R = n; continue; }                          // (one result per line)
+          rc = SampleDeviceWs(h, ws, ws->d_text.p, text_bytes, ws->d_offs.p, n, k, alpha, seed, line_base[c], s.d_ids.p, icap, s.d_io.p, st, &ti,
+                              piece ? s.d_sent.p : nullptr, piece ? s.d_nb.p : nullptr, piece ? s.d_ne.p : nullptr);
+        }
+        R = tr; T = ti;
+        if (rc != kResourceExhausted || (R <= rcap && T <= icap)) break;
+      }
+      if (rc != kOk) return rc;
+      s.results = R; s.total = T; s.image = 0;
+      if (piece) {
+        // device-form ranges -> the reference form the piece writer reads (kernels_latticecsr.h refspan); the device-form text
+        // and its offsets are where LatticeLaunch left them (d_norm, d_id_offs)
+        uint64_t dtotal = 0;
+        HIP_OR_RETURN(h, hipMemcpyAsync(&dtotal, ws->d_id_offs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_OR_RETURN(h, hipStreamSynchronize(st));
+        if (dtotal >= (1ull << 32) - 64) return Fail(h, kInvalidArgument, "more than 2^32 - 64 normalized bytes in one chunk");
+        HIP_OR_RETURN(h, s.d_flag.Reserve(dtotal + 1));
+        HIP_OR_RETURN(h, s.d_pre.Reserve(dtotal + 2));
+        HIP_OR_RETURN(h, s.d_rbase.Reserve(R + 1));
+        LatticeRefSpanArgs ra{};
+        ra.dnorm = ws->d_norm.p; ra.dnorm_bytes = dtotal; ra.flag = s.d_flag.p; ra.pre = s.d_pre.p; ra.id_offs = s.d_io.p; ra.R = R; ra.T = T;
+        ra.sent = s.d_sent.p; ra.dnoffs = ws->d_id_offs.p; ra.rnoffs = s.d_rnoffs.p; ra.nbegin = s.d_nb.p; ra.nend = s.d_ne.p;
+        ra.res_noffs = s.d_rbase.p;
+        const uint64_t wide = static_cast<uint64_t>(h->n_cu) * 16;
+        auto grid_of = [&](uint64_t units) { return static_cast<int>(units < 1 ? 1 : (units < wide ? units : wide)); };
+        if (dtotal) {
+          HIP_OR_RETURN(h, LaunchLatticeRefSpan(true, ra, grid_of((dtotal + 63) / 64), st));
+          HIP_OR_RETURN(h, ws->d_tile_sums.Reserve((dtotal + kScanTile - 1) / kScanTile + 2));
+          ScanArgs sa{s.d_flag.p, static_cast<uint32_t>(dtotal), ws->d_tile_sums.p, s.d_pre.p};
+          const uint32_t tiles = (static_cast<uint32_t>(dtotal) + kScanTile - 1) / kScanTile;
+          HIP_OR_RETURN(h, LaunchScan(sa, static_cast<int>(tiles < static_cast<uint32_t>(h->n_cu * 8) ? tiles : h->n_cu * 8), st));
+        } else {
+          HIP_OR_RETURN(h, hipMemsetAsync(s.d_pre.p, 0, sizeof(uint64_t), st));
+        }
+        if (R) HIP_OR_RETURN(h, LaunchLatticeRefSpan(false, ra, grid_of(std::max<uint64_t>((T + kLcRowChunk - 1) / kLcRowChunk, (R + 63) / 64)), st));
+        const PieceSource src{reinterpret_cast<const uint32_t *>(s.d_nb.p), reinterpret_cast<const uint32_t *>(s.d_ne.p), s.d_rnorm.p, s.d_rbase.p};
+        if (int r = TokenText(h, ws, 1, true, s.d_ids.p, s.d_io.p, R, T, &src, nullptr, nullptr, 0, &ws->d_tt_out, st, &s.image); r != kOk) return r;
+      } else if (int r = TokenText(h, ws, 0, true, s.d_ids.p, s.d_io.p, R, T, nullptr, nullptr, nullptr, 0, &ws->d_tt_out, st, &s.image); r != kOk) {
+        return r;
+      }
+      HIP_OR_RETURN(h, ws->h_text.Reserve(s.image + 32));
+      if (s.image) HIP_OR_RETURN(h, hipMemcpyAsync(ws->h_text.p, ws->d_tt_out.p, s.image, hipMemcpyDeviceToHost, st));
+      HIP_OR_RETURN(h, hipStreamSynchronize(st));
+      return kOk;
+    };
+    auto commit = [&](Scratch &s, uint64_t) -> int {
+      const bool ok = !s.image || fwrite(s.ws->h_text.p, 1, s.image, out.f) == s.image;
+      sent_total += s.n_lines;
+      line_total += s.results;
+      id_total += s.total;
+      return ok ? kOk : Fail(h, kDataLoss, "short write");
+    };
+    if (int rc = RunChunks<Scratch>(h, cut.size() - 1, true, process, commit); rc != kOk) return rc;
+    if (n_sentences) *n_sentences = sent_total;
+    if (n_lines) *n_lines = line_total;
     if (n_ids) *n_ids = id_total;
     return kOk;
   });
@@ -4372,4 +4822,5 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
 #include "../../tests/emu/emu_launch_idtext.h"
 #include "../../tests/emu/emu_launch_tokentext.h"
 #include "../../tests/emu/emu_launch_piececount.h"
+#include "../../tests/emu/emu_launch_latticecsr.h"
 #endif

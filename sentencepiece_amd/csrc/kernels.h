@@ -1382,6 +1382,7 @@ SPMX_DEVICE void compact_big_block(const CompactArgs &a) {
 #include "kernels_gather.h"
 #include "kernels_idtext.h"
 #include "kernels_tokentext.h"
+#include "kernels_latticecsr.h"
 #include "kernels_piececount.h"
 
 #endif

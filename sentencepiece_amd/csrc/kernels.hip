@@ -173,6 +173,14 @@ __global__ __launch_bounds__(64) void PieceLinesLenKernel(TokenTextArgs a) { tok
 __global__ __launch_bounds__(64) void PieceLinesWriteKernel(TokenTextArgs a) { token_write_block<1, true>(a); }
 __global__ __launch_bounds__(64) void PiecePackedLenKernel(TokenTextArgs a) { token_len_block<1, false>(a); }
 __global__ __launch_bounds__(64) void PiecePackedWriteKernel(TokenTextArgs a) { token_write_block<1, false>(a); }
+// lattice results -> dense CSR (kernels_latticecsr.h)
+__global__ __launch_bounds__(64) void LatticeCsrRowsKernel(LatticeCsrArgs a) { latticecsr_rows_block(a); }
+__global__ __launch_bounds__(64) void LatticeCsrGatherKernel(LatticeCsrArgs a) { latticecsr_gather_block(a); }
+__global__ __launch_bounds__(64) void LatticePickKernel(LatticePickArgs a) { latticecsr_pick_block(a); }
+__global__ __launch_bounds__(64) void LatticeMaxLenKernel(LatticeMaxLenArgs a) { latticecsr_maxlen_block(a); }
+__global__ __launch_bounds__(64) void LatticeSpFlagKernel(LatticeRefSpanArgs a) { latticecsr_spflag_block(a); }
+__global__ __launch_bounds__(64) void LatticeRefSpanKernel(LatticeRefSpanArgs a) { latticecsr_refspan_block(a); }
+__global__ __launch_bounds__(64) void LatticeIotaKernel(LatticeIotaArgs a) { latticecsr_iota_block(a); }
 // the id histogram (kernels_piececount.h): up to 128 KiB of bins, one workgroup per CU
 __global__ __launch_bounds__(64 * kCountMaxWaves) void CountIdsKernel(CountArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -390,6 +398,29 @@ hipError_t LaunchTokenText(int fmt, bool lines, bool write, const TokenTextArgs 
                 : lines  ? (write ? PieceLinesWriteKernel : PieceLinesLenKernel)
                          : (write ? PiecePackedWriteKernel : PiecePackedLenKernel);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t LaunchLatticeCsr(bool gather, const LatticeCsrArgs &a, int grid, hipStream_t stream) {
+  if (gather) hipLaunchKernelGGL(LatticeCsrGatherKernel, dim3(grid), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(LatticeCsrRowsKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t LaunchLatticePick(const LatticePickArgs &a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(LatticePickKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t LaunchLatticeMaxLen(const LatticeMaxLenArgs &a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(LatticeMaxLenKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t LaunchLatticeRefSpan(bool flags, const LatticeRefSpanArgs &a, int grid, hipStream_t stream) {
+  if (flags) hipLaunchKernelGGL(LatticeSpFlagKernel, dim3(grid), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(LatticeRefSpanKernel, dim3(grid), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+hipError_t LaunchLatticeIota(const LatticeIotaArgs &a, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(LatticeIotaKernel, dim3(grid), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -42,7 +42,8 @@ struct LongArgs {
   int32_t *arena_tb;            // spans form, else null
   uint32_t stack_cap;           // entries of the resegmentation stack (> longest piece in characters)
   float dropout;                // BPE-dropout (src/bpe_model.cc:131-156): a valid merge is skipped with this probability
-  uint64_t seed;                // ... by a generator keyed by (seed, sentence index)
+  uint64_t seed;                // ... by a generator keyed by (seed, index_base + sentence index)
+  uint64_t index_base;
   unsigned long long *stats;    // (wave-cooperative unigram form, nullable) kStatsPerClass words as EncodeArgs::stats
 };
 
@@ -230,7 +231,7 @@ SPMX_DEVICE void bpe_long_lane(const LongArgs &a, uint32_t sid, uint8_t *rawwin)
   };
   for (uint32_t p = 0; p < N; p = nxt[p]) add_pair(p);               // :127-129
   // ---- main loop (:142-173) ----
-  unsigned long long rng = a.seed * 0x9E3779B97F4A7C15ull + (static_cast<unsigned long long>(sid) + 1ull) * 0xD1B54A32D192ED03ull;
+  unsigned long long rng = a.seed * 0x9E3779B97F4A7C15ull + (a.index_base + static_cast<unsigned long long>(sid) + 1ull) * 0xD1B54A32D192ED03ull;
   while (hn > 0) {
     const U4 top = agenda_pop(heap, &hn);
     const uint32_t l = top.y;

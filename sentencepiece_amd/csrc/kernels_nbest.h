@@ -54,6 +54,8 @@ struct NBestArgs {
   float inv_theta;              // modes 1, 3, 4, 5
   uint64_t seed;                // mode 1: the lanes' generators are keyed by (seed, sentence index); mode 4: draw j of
                                 // sentence i by (hash of the seed, i, j); mode 5: (hash of the seed, sentence index)
+  uint64_t index_base;          // the sentence index of those keys is index_base + s: a batch that is rows [k, n) of a larger
+                                // one draws what the larger one draws for them (0: the batch's own numbering)
   uint8_t *scratch;             // [lanes of the launch][lane_bytes]
   uint64_t lane_bytes;
   uint32_t max_hyps;
@@ -405,7 +407,7 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
       alpha[pos] = acc;
     }
     // keyed by (seed, sentence)
-    st = a.seed * 0x9E3779B97F4A7C15ull + (static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull;
+    st = a.seed * 0x9E3779B97F4A7C15ull + (a.index_base + static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull;
     const uint32_t first = draw_path(alpha);
     emit_path([&] { return first; }, [&](uint32_t h) { return nodes[h].prev; }, [&](uint32_t h) { return h == 1u; }, 0.f);
     return;
@@ -460,7 +462,7 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     const float marginal = alpha[len];
     const unsigned long long hs = hashed_seed();
     for (uint32_t j = 0; j < a.nbest; ++j) {
-      st = hs + (static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull +
+      st = hs + (a.index_base + static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull +
            (static_cast<unsigned long long>(j) + 1ull) * 0xA0761D6478BD642Full;
       const uint32_t first = draw_path(alpha);
       float score = 0.f;
@@ -533,7 +535,7 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
       nodes[nd].backtrace = acc;
     }
     marginal = nodes[1].backtrace;
-    st = hashed_seed() + (static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull + 0x8EBC6AF09C88C6E3ull;
+    st = hashed_seed() + (a.index_base + static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull + 0x8EBC6AF09C88C6E3ull;
   }
   // Gumbel() (:61-70): -log(-log(u + 1e-7f)) in float, u uniform over the 2^24 floats k / 2^24.  Where u + 1e-7f rounds to
   // 1 the reference returns +inf (two values of u); those are drawn again here.

@@ -77,6 +77,13 @@ hipError_t LaunchJoinLines(const JoinLinesArgs &a, int grid, hipStream_t stream)
 // the file side of Encode (kernels_tokentext.h): fmt 0 decimal ids (lines only) / 1 pieces, the lines or the packed form,
 // the length pass or the write pass
 hipError_t LaunchTokenText(int fmt, bool lines, bool write, const TokenTextArgs &a, int grid, hipStream_t stream);
+// lattice results -> dense CSR (kernels_latticecsr.h): the rows pass or the gather pass; the pick of SampleEncode's n-best
+// branch; the arrays of a call that went to the plain encoder
+hipError_t LaunchLatticeCsr(bool gather, const LatticeCsrArgs &a, int grid, hipStream_t stream);
+hipError_t LaunchLatticePick(const LatticePickArgs &a, int grid, hipStream_t stream);
+hipError_t LaunchLatticeMaxLen(const LatticeMaxLenArgs &a, int grid, hipStream_t stream);
+hipError_t LaunchLatticeRefSpan(bool flags, const LatticeRefSpanArgs &a, int grid, hipStream_t stream);   // the flags pass or the conversion
+hipError_t LaunchLatticeIota(const LatticeIotaArgs &a, int grid, hipStream_t stream);
 // the id histogram (kernels_piececount.h): workgroups of `waves` <= kCountMaxWaves wavefronts, a.bins * 4 bytes of LDS each
 hipError_t LaunchCountIds(const CountArgs &a, int grid, int waves, hipStream_t stream);
 

@@ -1632,6 +1632,82 @@ class SentencePieceProcessor:
         out = [ids[io[i]:io[i + 1]].tolist() for i in range(len(bs))]
         return out[0] if single else out
 
+    # ------------------------------------- lattice calls on device tensors ----
+    def _lattice_device(self, d_text, d_offsets, per_sentence, stream, call):
+        """The capacity protocol of the n-best device forms, one retry: ``call(ids, ids_cap, id_offsets, scores, sent,
+        results_cap, result_offsets, stream, total_results, total_ids)`` -> rc."""
+        import torch
+        self._need()
+        self._apply(False, False, False)
+        n = d_offsets.numel() - 1
+        dev = d_text.device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        rcap = n * min(max(int(per_sentence), 1), 8) + 64
+        icap = self._ids_guess(d_text.numel(), n) * min(max(int(per_sentence), 1), 8)
+        d_ro = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        tr, ti = C.c_uint64(0), C.c_uint64(0)
+        for _ in range(2):
+            d_ids = torch.empty(max(icap, 1), dtype=torch.int32, device=dev)
+            d_io = torch.empty(rcap + 1, dtype=torch.int64, device=dev)
+            d_sc = torch.empty(max(rcap, 1), dtype=torch.float32, device=dev)
+            d_sent = torch.empty(max(rcap, 1), dtype=torch.int32, device=dev)      # (uint32 values: a batch has < 2^31 sentences here)
+            rc = call(d_ids.data_ptr(), icap, d_io.data_ptr(), d_sc.data_ptr(), d_sent.data_ptr(), rcap, d_ro.data_ptr(), stream,
+                      C.byref(tr), C.byref(ti))
+            if rc == _RESOURCE_EXHAUSTED and (tr.value > rcap or ti.value > icap):
+                rcap, icap = max(rcap, tr.value), max(icap, ti.value)
+                continue
+            break
+        self._check(rc)
+        R, T = tr.value, ti.value
+        return d_ids[:T], d_io[:R + 1], d_sc[:R], d_ro, d_sent[:R]
+
+    def NBestEncodeDevice(self, d_text, d_offsets, nbest_size, stream=None):
+        """``NBestPacked`` over torch tensors on this processor's GPU, the results left there: ``d_text`` uint8[bytes],
+        ``d_offsets`` int64[n + 1] -> ``(ids int32[T], id_offsets int64[R + 1], scores float32[R], result_offsets
+        int64[n + 1], sent_of_result int32[R])``.  Sentence s owns the results ``result_offsets[s]:result_offsets[s + 1]``,
+        best first; ``sent_of_result[r]`` is the sentence of result r."""
+        return self._lattice_device(d_text, d_offsets, nbest_size, stream, lambda *a: self._lib.spmx_nbest_encode_batch_device(
+            self._h, d_text.data_ptr(), d_text.numel(), d_offsets.data_ptr(), d_offsets.numel() - 1, int(nbest_size), *a))
+
+    def SampleEncodeAndScoreDevice(self, d_text, d_offsets, num_samples=1, alpha=1.0, wor=False, include_best=False, seed=0,
+                                   stream=None):
+        """``SampleEncodeAndScorePacked`` over torch tensors, the results left on the GPU: the five tensors of
+        ``NBestEncodeDevice``.  A sentence without a result owns an empty range of ``result_offsets``."""
+        return self._lattice_device(d_text, d_offsets, int(num_samples) + 1, stream,
+                                    lambda *a: self._lib.spmx_sample_encode_and_score_batch_device(
+                                        self._h, d_text.data_ptr(), d_text.numel(), d_offsets.data_ptr(), d_offsets.numel() - 1,
+                                        int(num_samples), C.c_float(alpha), int(bool(wor)), int(bool(include_best)), int(seed), *a))
+
+    def SampleEncodeDevice(self, d_text, d_offsets, nbest_size=-1, alpha=0.1, seed=0, index_base=0, d_ids=None, d_id_offsets=None,
+                           stream=None):
+        """``SampleEncodePacked`` over torch tensors, for sampling inside a training step: the ids stay on the GPU.
+        Returns ``(d_ids, d_id_offsets int64[n + 1], total)`` as ``EncodeDevice`` does; a too-small ``d_ids`` is
+        allocated again once.  The draws of sentence s are keyed by ``(seed, index_base + s)``: a batch that is rows
+        ``[k, n)`` of a larger one, run with ``index_base=k``, draws what the larger one draws for them."""
+        import torch
+        self._need()
+        self._apply(False, False, False)
+        n = d_offsets.numel() - 1
+        dev = d_text.device
+        if d_id_offsets is None:
+            d_id_offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if d_ids is None:
+            d_ids = torch.empty(self._ids_guess(d_text.numel(), n), dtype=torch.int32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        total = C.c_uint64(0)
+        for _ in range(2):
+            rc = self._lib.spmx_sample_encode_batch_device(
+                self._h, d_text.data_ptr(), d_text.numel(), d_offsets.data_ptr(), n, int(nbest_size), C.c_float(alpha), int(seed),
+                int(index_base), d_ids.data_ptr(), d_ids.numel(), d_id_offsets.data_ptr(), stream, C.byref(total))
+            if rc == _RESOURCE_EXHAUSTED and total.value > d_ids.numel():
+                d_ids = torch.empty(total.value, dtype=torch.int32, device=dev)
+                continue
+            break
+        self._check(rc)
+        return d_ids, d_id_offsets, total.value
+
     def EncodeOriginalPacked(self, text, offsets):
         """The reference's kOriginal unigram encoder (Lattice::Viterbi, src/unigram_model.cc:161-198, :674-692) per
         sentence -> CSR ``(ids, id_offsets)``."""
@@ -1639,15 +1715,33 @@ class SentencePieceProcessor:
         self._apply(False, False, False)
         return self._csr_call(self._lib.spmx_encode_batch_original, text, offsets)
 
-    def EncodeFile(self, in_path, out_path, output_format="id"):
+    def EncodeFile(self, in_path, out_path, output_format="id", nbest_size=10, alpha=0.5, seed=None):
         """Corpus file -> ids or pieces, the loop of the reference's ``spm_encode`` (spm_encode_main.cc:110-165) as one
         pipelined call: ``output_format="id"`` writes the text of ``--output_format=id`` (one line of space-separated ids
         per input line), ``"piece"`` that of ``--output_format=piece``, the reference's default (the pieces joined with
         ``' '``), ``"bin"`` the flat int32 ids to ``out_path`` and the uint64 offsets to ``out_path + ".idx"``.
-        ``SetEncodeExtraOptions`` applies.  Returns ``(sentences, ids)``."""
+        ``SetEncodeExtraOptions`` applies.  Returns ``(sentences, ids)``.
+
+        The lattice formats of ``spm_encode`` go through ``spmx_encode_file_ex`` and return ``(sentences, lines, ids)``:
+        ``"nbest_id"`` / ``"nbest_piece"`` write one line of ids / pieces per result of ``NBestEncode(line, nbest_size)``,
+        ``"sample_id"`` / ``"sample_piece"`` one line per input line from ``SampleEncode(line, nbest_size, alpha)``, its
+        draws keyed by ``(seed, line number)`` -- the file's lines are what ``SampleEncodePacked`` / ``SampleEncodeAsPieces``
+        give for them with the same seed; ``seed=None`` counts up per call, as the other sampling methods do.  ``"proto"``,
+        ``"sample_proto"`` and ``"nbest_proto"`` leave an empty file, as the reference does."""
         self._need()
         self._apply(False, False, False)
         ns, ni = C.c_uint64(0), C.c_uint64(0)
+        if output_format not in ("id", "piece", "bin"):
+            if seed is None:
+                if not hasattr(self, "_sample_calls"):
+                    self._sample_calls = int.from_bytes(os.urandom(7), "little")
+                self._sample_calls += 1
+                seed = self._sample_calls
+            nl = C.c_uint64(0)
+            self._check(self._lib.spmx_encode_file_ex(self._h, os.fsencode(in_path), os.fsencode(out_path), output_format.encode(),
+                                                      int(nbest_size), C.c_float(alpha), int(seed), C.byref(ns), C.byref(nl),
+                                                      C.byref(ni)))
+            return int(ns.value), int(nl.value), int(ni.value)
         self._check(self._lib.spmx_encode_file(self._h, os.fsencode(in_path), os.fsencode(out_path),
                                                output_format.encode(), C.byref(ns), C.byref(ni)))
         return int(ns.value), int(ni.value)

@@ -1,8 +1,12 @@
 // spmx_encode: the command line of the reference's spm_encode (src/spm_encode_main.cc) over the C ABI of include/spmx.h:
 // file (or stdin) in; out one line of space-separated ids per input line (--output_format=id, the reference's bytes), one
 // line of space-separated pieces (--output_format=piece, the reference's bytes for its default format), or flat binary
-// ids (--output_format=bin).  The default here is id; the reference's is piece.
-//   spmx_encode --model=M [--input=F] [--output=F] [--output_format=id|piece|bin] [--extra_options=bos:eos] [--device=N]
+// ids (--output_format=bin).  The default here is id; the reference's is piece.  --output_format also takes the reference's
+// other names: nbest_id / nbest_piece (one line per result of NBestEncode(line, --nbest_size)), sample_id / sample_piece
+// (SampleEncode(line, --nbest_size, --alpha), the draws keyed by --random_seed and the line number), proto / sample_proto /
+// nbest_proto (nothing is written, as in the reference).
+//   spmx_encode --model=M [--input=F] [--output=F] [--output_format=id|piece|bin|nbest_id|nbest_piece|sample_id|sample_piece|...] [--nbest_size=10]
+//               [--alpha=0.5] [--random_seed=N] [--extra_options=bos:eos] [--device=N]
 //               [--vocabulary=F --vocabulary_threshold=N] [--generate_vocabulary [FILE ...]]
 // --vocabulary / --vocabulary_threshold restrict the pieces before any mode (LoadVocabulary, :80-83).
 // --generate_vocabulary (bare or =true|false) writes `piece TAB count` lines instead of a segmentation (:102-109,
@@ -12,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <string>
 #include <vector>
 #include <unistd.h>
@@ -21,9 +26,14 @@
 int main(int argc, char **argv) {
   std::string model, input, output, format = "id", extra, vocabulary;
   std::vector<std::string> rest;
-  int device = 0, vocabulary_threshold = 0;
+  int device = 0, vocabulary_threshold = 0, nbest_size = 10;     // (--nbest_size 10, --alpha 0.5: src/spm_encode_main.cc:50-52)
+  float alpha = 0.5f;
+  unsigned long long random_seed = ~0ull;                       // (the reference: "~0u" means the seed is not set)
+  bool seed_set = false;
   bool generate = false;
-  const char *usage = "usage: spmx_encode --model=M [--input=F] [--output=F] [--output_format=id|piece|bin] [--extra_options=..] "
+  const char *usage = "usage: spmx_encode --model=M [--input=F] [--output=F] [--extra_options=..] [--device=N]\n"
+                      "       [--output_format=id|piece|bin|nbest_id|nbest_piece|sample_id|sample_piece|proto|nbest_proto|sample_proto]\n"
+                      "       [--nbest_size=10] [--alpha=0.5] [--random_seed=N]\n       "
                       "[--vocabulary=F --vocabulary_threshold=N] [--generate_vocabulary [FILE ...]]\n"
                       "       (several positional inputs only with --generate_vocabulary)\n";
   for (int i = 1; i < argc; ++i) {
@@ -43,6 +53,9 @@ int main(int argc, char **argv) {
     }
     if (val("vocabulary", &vocabulary)) continue;
     if (val("vocabulary_threshold", &flag)) { vocabulary_threshold = atoi(flag.c_str()); continue; }
+    if (val("nbest_size", &flag)) { nbest_size = atoi(flag.c_str()); continue; }
+    if (val("alpha", &flag)) { alpha = static_cast<float>(atof(flag.c_str())); continue; }
+    if (val("random_seed", &flag)) { random_seed = strtoull(flag.c_str(), nullptr, 10); seed_set = true; continue; }
     if (val("model", &model) || val("input", &input) || val("output", &output) || val("output_format", &format) ||
         val("extra_options", &extra)) continue;
     if (val("device", &dev)) { device = atoi(dev.c_str()); continue; }
@@ -89,7 +102,8 @@ int main(int argc, char **argv) {
     }
     if (rc == 0) rc = spmx_write_vocabulary(h, counts.data(), out_path.c_str(), nullptr);
   } else {
-    rc = spmx_encode_file(h, in_path.c_str(), out_path.c_str(), format.c_str(), &ns, &ni);
+    if (!seed_set) random_seed = static_cast<unsigned long long>(getpid()) * 0x9E3779B97F4A7C15ull ^ static_cast<unsigned long long>(time(nullptr));
+    rc = spmx_encode_file_ex(h, in_path.c_str(), out_path.c_str(), format.c_str(), nbest_size, alpha, random_seed, &ns, nullptr, &ni);
   }
   if (rc != 0) fprintf(stderr, "%s\n", spmx_last_error(h));
   if (rc == 0 && output.empty()) {
