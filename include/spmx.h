@@ -622,9 +622,10 @@ int spmx_load_vocabulary(spmx_handle *h, const char *path, int threshold);
  * sentence-per-wave BPE launches, 4 the long form (the wave-cooperative unigram form included), 5 the first round of the
  * word form, 6 its second round; unused slots are zero); returns the number of slots (callers size for 8).
  * spmx_last_profile_name() gives the kernel symbol of a slot as rocprofv3 prints it.  bytes[] is the algorithmic
- * byte count SURVEY.md section 8d defines (raw bytes + 8 + 4 * ids + 8 per sentence).  path[6]: sentences the main
+ * byte count SURVEY.md section 8d defines (raw bytes + 8 + 4 * ids + 8 per sentence).  path[8]: sentences the main
  * tiles set aside on hard lists, sentences on the overflow list, sentences that took the long form, failed sentences,
- * times the call encoded the batch again because the id arena was too small, launches of the long form (slot 4). */
+ * times the call encoded the batch again because the id arena was too small, launches of the long form (slot 4),
+ * wavefronts per workgroup of the word-per-lane form's first and of its second round (0: the round did not take that form). */
 int spmx_set_profiling(spmx_handle *h, int enabled);
 int spmx_last_profile_name(const spmx_handle *h, int slot, char *out, uint64_t cap);
 int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentences, uint64_t *raw_bytes,

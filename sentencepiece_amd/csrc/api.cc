@@ -383,7 +383,8 @@ struct spmx_handle : DevTables {
   uint64_t dn_table_bytes = 0;   // ... of which the denormalizer's
   double load_ms = 0.0;          // parse + table build + upload, wall clock
   int word_form = 3;             // SPMX_WORD_WAVE: which word rounds take the word-per-lane form (kernels_wordwave.h): bit 0 the first, bit 1 the second; 0: the sentence-per-lane loops
-  int wordwave_waves = 14;       // SPMX_WORDWAVE_WAVES: wavefronts per workgroup of the word-per-lane kernels (C2's first round: 8 -> 3.71 ms, 10 -> 3.31, 12 -> 3.08, 13 -> 3.02, 14 -> 2.96, 15 -> 2.94 with a worse step; 14 x 10 KB + the shared tables = 153 KB of LDS)
+  int wordwave_waves = 16;       // SPMX_WORDWAVE_WAVES: wavefronts per workgroup of the word-per-lane kernels (C2's first round, round-6 kernels: 8 -> 3.71 ms, 10 -> 3.31, 12 -> 3.08, 13 -> 3.02, 14 -> 2.96, 15 -> 2.94 with a worse step; round 15's, every tile from the cursor: 12 -> 2.84, 14 -> 2.77, 15 -> 2.73, 16 -> 2.73; with 7/8 of the tiles by index: 12 -> 2.61, 14 -> 2.52, 15 -> 2.51, 16 -> 2.48 and the step 3.83 -> 3.79 ms from 14 to 16, profiles/r15_word_waves_ab.txt).  The first round's own LDS layout (kernels_wordwave.h: 8,832 B shared + 9,520 B a wavefront) puts 16 into a CU's 160 KB -- four per SIMD, the last step its registers allow (108; a fifth per SIMD needs 96 and LDS the CU does not have); the second round keeps its bound of kWwAgainMaxWaves
+  double static_tiles_frac = 0.875;   // SPMX_STATIC_TILES (0 .. 1): share of a direct first word round's tiles its wavefronts take by their own index instead of from the queue's cursor (kernels_wordwave.h ww_next_tile), rounded down to whole rounds of the launch's wavefronts; 0: every tile from the cursor (C2 step at 0 / 1/2 / 3/4 / 7/8: 4.05 / 3.80 / 3.78 / 3.77 ms, a second box 4.04 / 3.79 / 3.79 / 3.79; not length-bucketed 3.99 -> 3.95; profiles/r15_word_waves_ab.txt)
   int word_waves = 12;           // SPMX_WORD_WAVES: wavefronts per workgroup of the word kernels (C2 step: 16 -> 8.60 ms, 14 -> 8.39, 12 -> 8.37, 10 -> 8.52, 8 -> 8.90)
   int tile_waves_override = 0;   // SPMX_TILE_WAVES: cap on wavefronts per workgroup of the streaming kernels
   uint32_t lane_general_min_lanes = 0;   // SPMX_LANE_GENERAL_MIN_LANES (0: per class)
@@ -916,6 +917,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       (direct ? (ws->reserve_text_bytes + (1 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * (ws->reserve_n > n ? ws->reserve_n : n)) / (ids16 ? 2 : 1) + 8 : 0);
   for (int attempt = 0; attempt < 4; ++attempt) {
     uint64_t long_launches = 0;             // launches of the long form in this attempt (Profile::path[5])
+    uint64_t word_waves[2] = {0, 0};        // wavefronts per workgroup of the word-per-lane rounds' launches (Profile::path[6], [7]; 0: not launched)
     HIP_OR_RETURN(h, ws->d_arena.Reserve(arena_need > arena_reserve ? arena_need : arena_reserve));
     if (spans) HIP_OR_RETURN(h, ws->d_arena_tb.Reserve(ws->d_arena.cap));
     if (prof) HIP_OR_RETURN(h, hipEventRecord(ws->ev[kNumSlots][0], stream));
@@ -1222,7 +1224,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
           const uint64_t per_cu = (gt + static_cast<uint64_t>(h->n_cu) - 1) / static_cast<uint64_t>(h->n_cu);
           stream_waves_cap = h->fork_waves ? h->fork_waves : static_cast<int>(per_cu < 4 ? 4 : (per_cu > 12 ? 12 : per_cu));
           stream_cus_cap = h->fork_cus;
-          // Beside the word-per-lane round (kernels_wordwave.h: 12 wavefronts and 156 KB of LDS per workgroup) nothing
+          // Beside the word-per-lane round (kernels_wordwave.h: 16 wavefronts and 157 KB of LDS per workgroup; 12 and 156 KB when this was measured) nothing
           // else fits a CU: the general launch gets CUs of its own instead -- 32 of them at full width (it is bound by
           // the latency of its longest sentences: 2.7 ms there against 2.3 ms on all 256), the word round the others and,
           // when those workgroups end, these (C2: 6.65 ms a step against 8.4 with 4 wavefronts on every CU;
@@ -1275,7 +1277,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
         const bool wform = !dp && ((mode == 2 ? h->word_form & 2 : h->word_form & 1) != 0);   // word per lane
         int waves = dp ? 8 : wform ? h->wordwave_waves : h->word_waves;
         if (wform && mode == 2 && waves > static_cast<int>(kWwAgainMaxWaves)) waves = static_cast<int>(kWwAgainMaxWaves);   // (the second round's launch bound: three wavefronts per SIMD, its pipeline in registers)
-        while (wform && waves > 1 && WordWaveLdsBytes(static_cast<uint32_t>(waves)) > 160u * 1024u) --waves;   // (a CU's LDS: an A/B build with a larger hot table)
+        while (wform && waves > 1 && WordWaveLdsBytes(mode, static_cast<uint32_t>(waves)) > 160u * 1024u) --waves;   // (a CU's LDS: an A/B build with a larger hot table)
         uint64_t total = 0;
         for (int c = 0; c < ncls; ++c) total += known[c];
         if (total == 0) return kOk;
@@ -1319,6 +1321,11 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
           tile_base += sc.main_tiles;
         }
         wa.total_main = tile_base;
+        // (direct first round, word per lane) the first tiles by the wavefront's index, the last from the cursor
+        wa.static_tiles = 0;
+        wa.static_stride = static_cast<uint32_t>(n_waves);
+        if (wform && direct && mode != 2 && h->static_tiles_frac > 0.0)
+          wa.static_tiles = static_cast<uint32_t>(static_cast<uint64_t>(h->static_tiles_frac * static_cast<double>(tile_base)) / n_waves * n_waves);
         wa.q = &ws->d_ctrl->q[qi];
         wa.stats = &ws->d_ctrl->stats[kStatsPerClass * slot];
         wa.left_lists = out_lists;
@@ -1338,8 +1345,9 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
                  wform ? (wa.ids16 ? (mode == 2 ? "EncodeWordWaveAgainKernel<true>" : mode == 1 ? "EncodeWordWaveCollectKernel<true>" : "EncodeWordWaveKernel<true>")
                                    : (mode == 2 ? "EncodeWordWaveAgainKernel<false>" : mode == 1 ? "EncodeWordWaveCollectKernel<false>" : "EncodeWordWaveKernel<false>"))
                        : mode == 3 ? "EncodeWordDpKernel" : mode == 2 ? "EncodeWordAgainKernel" : mode == 1 ? "EncodeWordCollectKernel" : "EncodeWordKernel");
+        if (wform) word_waves[mode == 2 ? 1 : 0] = static_cast<uint64_t>(waves);
         HIP_OR_RETURN(h, record(slot, 0));
-        if (wform) HIP_OR_RETURN(h, LaunchEncodeWordWave(mode, wa, static_cast<int>(grid), waves, WordWaveLdsBytes(waves), stream));
+        if (wform) HIP_OR_RETURN(h, LaunchEncodeWordWave(mode, wa, static_cast<int>(grid), waves, WordWaveLdsBytes(mode, static_cast<uint32_t>(waves)), stream));
         else HIP_OR_RETURN(h, LaunchEncodeWord(mode, wa, static_cast<int>(grid), waves, WordLdsBytes(waves, dp), stream));
         HIP_OR_RETURN(h, record(slot, 1));
         ws->slot_used[slot] = true;
@@ -1506,6 +1514,7 @@ int EncodeDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t 
       p.path[3] = ws->h_ctrl->side.n_failed;
       p.path[4] = static_cast<uint64_t>(attempt);   // (encodes of the batch again with a larger arena)
       p.path[5] = long_launches;
+      p.path[6] = word_waves[0]; p.path[7] = word_waves[1];
       HIP_OR_RETURN(h, hipEventElapsedTime(&p.total_ms, ws->ev[kNumSlots][0], ws->ev[kNumSlots][1]));
       std::lock_guard<std::mutex> l(h->mu);
       h->prof = p;
@@ -2003,6 +2012,7 @@ int spmx_create(const void *model_bytes, uint64_t n_bytes, int device, spmx_hand
     if (const char *e = getenv("SPMX_UNI_WAVE_MAX")) h->uni_wave_max = static_cast<uint32_t>(atoll(e));
     if (const char *e = getenv("SPMX_WORD_WAVE")) { const int v = atoi(e); if (v >= 0 && v <= 3) h->word_form = v; }
     if (const char *e = getenv("SPMX_WORDWAVE_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 16) h->wordwave_waves = v; }
+    if (const char *e = getenv("SPMX_STATIC_TILES")) { const double v = atof(e); if (v >= 0.0 && v <= 1.0) h->static_tiles_frac = v; }
     if (const char *e = getenv("SPMX_WORD_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 16) h->word_waves = v; }
     if (const char *e = getenv("SPMX_ARENA_FIRST")) h->arena_first = static_cast<uint64_t>(atoll(e));
     if (const char *e = getenv("SPMX_NO_LANE_GENERAL")) h->no_lane_general = e[0] == '1';
@@ -4809,7 +4819,7 @@ int spmx_last_profile(const spmx_handle *h, float *kernel_ms, uint64_t *sentence
     // L + 8 + 4 T' + 8 per sentence
     if (bytes) bytes[c] = p.raw_bytes[c] + 16 * p.sentences[c] + 4 * p.ids[c];
   }
-  if (path) for (int k = 0; k < 6; ++k) path[k] = p.path[k];
+  if (path) for (int k = 0; k < 8; ++k) path[k] = p.path[k];
   if (total_ms) *total_ms = p.total_ms;
   return p.n;
 }

@@ -124,6 +124,10 @@ struct EncodeArgs {
   // (direct, first round) int32 entries at the arena's start that hold the first round's tile regions (sentence s of the
   // batch from id unit offs[s] - offs[0] + s * (1 + n_prefix + n_suffix)); arena_head is moved past them once per launch
   uint64_t arena_first;
+  // (direct first round) the launch's first static_tiles tiles are taken by index -- wavefront g of the launch's n_waves
+  // takes g, g + n_waves, ... -- and only the tiles behind them from q->main_cursor (kernels_wordwave.h ww_next_tile); a
+  // multiple of static_stride = n_waves = workgroups x wavefronts per workgroup, at most total_main; 0: every tile from the cursor
+  uint32_t static_tiles, static_stride;
   // ---- sentence-per-wave launch (BPE models that are not word-wise; kernels_bpe.h) ----
   const uint32_t *list;         // sentence indices of this length class
   const uint32_t *list_count;   // number of entries in list (device resident)

@@ -50,8 +50,13 @@ constexpr uint32_t kWwUnits = kWwRing / 16u;        // 256
 constexpr uint32_t kWwMaskBytes = (kWwUnits + 4u) * 2u + 8u;   // a 16-bit space mask per unit (+ the first four again behind the end)
 constexpr uint32_t kWwRecs = 128u + 512u;           // the word queue: what the last round left (< 128) + at most 8 starts per unit
 constexpr uint32_t kWwMaxLen = 65536u;              // longer sentences are not taken (record positions have 26 bits)
-constexpr uint32_t kWwPerWave = kWwRing + kWwRingPad + kWwMaskBytes + kWwRecs * 4u + 64u * 16u + 64u * 8u + 5u * 64u * 4u;
-static_assert(kWwPerWave % 16u == 0u, "per-wave LDS blocks keep 16-byte alignment");
+// a wavefront's LDS by mode: ring, space masks, word queue, the tile's sentences {sent, sent_ua, s_nids, s_stat, s_first} and,
+// in the second round only, where each sentence is taken up {s_n0, s_x0}: 9,520 B (first round) / 10,032 B (second round)
+SPMX_HD constexpr uint32_t kWwPerWave(int mode) {
+  return kWwRing + kWwRingPad + kWwMaskBytes + kWwRecs * 4u + 64u * 16u + 64u * 8u + 3u * 64u * 4u + (mode == 2 ? 2u * 64u * 4u : 0u);
+}
+static_assert(kWwPerWave(0) % 16u == 0u && kWwPerWave(1) % 16u == 0u && kWwPerWave(2) % 16u == 0u,
+              "per-wave LDS blocks keep 16-byte alignment");
 constexpr uint32_t kWwAgainMaxWaves = 12u;          // wavefronts per workgroup of the second round (its launch bound, kernels.hip)
 constexpr uint32_t kWwAgain = 1u, kWwGone = 2u;     // per-sentence status bits
 constexpr uint32_t kWwKeyMaskBytes = 640u;          // 18 rows {key mask, padding under the mask's zeros} of 32 bytes (+ slack)
@@ -60,10 +65,14 @@ constexpr uint32_t kWwKeyMaskBytes = 640u;          // 18 rows {key mask, paddin
 // bytes a word).  The first round dropped it in round 6: a word the table lacks is answered by `uall` from L2, every lane
 // issues that probe anyway, and the table's lookup was ~25 instructions per 64 words of an issue-bound loop -- 2048 / 1024 /
 // 512 slots: 3.085 / 3.076 / 3.067 ms, none: 2 % faster still; with all words asking the call-local memo the second round
-// is 12 % slower on open-vocabulary text (profiles/r06_hot_slots_waves.txt).  Same LDS layout for every mode.
-constexpr uint32_t kWwShared = kWwKeyMaskBytes + kWordHotSlots * 16u + kUallBuckets * 2u;
+// is 12 % slower on open-vocabulary text (profiles/r06_hot_slots_waves.txt).
+// The LDS layout follows the mode: a round holds only what it reads.  The second round's is {key masks, table of likely
+// words, displacements} + 10,032 B a wavefront; the first round's has neither the table nor s_n0 / s_x0: 8,832 B shared +
+// 9,520 B a wavefront, so that 16 wavefronts (four per SIMD) fit a CU's 160 KB: 8,832 + 16 x 9,520 = 161,152 B.
 SPMX_HD constexpr bool kWwHotIn(int mode) { return mode == 2; }      // (kWmDyn)
-SPMX_HD inline uint32_t WordWaveLdsBytes(uint32_t waves) { return kWwShared + waves * kWwPerWave; }
+SPMX_HD constexpr uint32_t kWwShared(int mode) { return kWwKeyMaskBytes + (kWwHotIn(mode) ? kWordHotSlots * 16u : 0u) + kUallBuckets * 2u; }
+static_assert(kWwShared(0) % 16u == 0u && kWwShared(2) % 16u == 0u, "the shared tables keep 16-byte alignment");
+SPMX_HD inline uint32_t WordWaveLdsBytes(int mode, uint32_t waves) { return kWwShared(mode) + waves * kWwPerWave(mode); }
 
 struct __attribute__((packed, aligned(2))) U64H { uint32_t lo, hi; };   // 8 bytes at any 2-byte address
 
@@ -121,21 +130,44 @@ struct WwStage {
 };
 constexpr uint32_t kWwHit16 = 0x100u;
 
+// The wavefront's next tile, in every lane.  A direct first round's first a.static_tiles tiles follow from the wavefront's
+// own index: wavefront g of the launch's n_waves takes tiles g, g + n_waves, ... below static_tiles (a multiple of n_waves)
+// from a loop counter -- no memory operation, nothing in flight, one scalar held -- and after them static_tiles + the
+// queue's cursor, as next_tile (kernels_stream.h) hands tiles out.  Every index is taken exactly once, no wavefront waits
+// for another.  On a batch sorted by length the tiles taken by index are the short ones; the long last tiles keep the queue,
+// where the balance matters.
+// -> {got, class, first, count}; the caller moves own_tile on by a.static_stride where it was below a.static_tiles
+template <int MODE>
+SPMX_DEVICE U4 ww_next_tile(const EncodeArgs &a, int lane, uint32_t own_tile) {
+  uint32_t t = own_tile;
+  if (MODE == kWmDyn || own_tile >= a.static_tiles) {               // (wave-uniform)
+    uint32_t v = 0;
+    if (lane == 0) v = wv::atomic_add(&a.q->main_cursor, 1u);
+    t = wv::uniform((MODE != kWmDyn ? a.static_tiles : 0u) + wv::shfl(v, 0));
+  }
+  if (t >= a.total_main) return U4{0u, 0u, 0u, 0u};
+  int k = static_cast<int>(a.n_classes) - 1;                        // (the classes are laid out longest first in the cursor's range)
+  while (k > 0 && !(t >= a.cls[k].tile_base && t - a.cls[k].tile_base < a.cls[k].main_tiles)) --k;
+  const uint32_t first = (t - a.cls[k].tile_base) * a.cls[k].tw, left = a.cls[k].count - first;
+  return U4{1u, static_cast<uint32_t>(k), first, left < a.cls[k].tw ? left : a.cls[k].tw};
+}
+
 template <int MODE, bool H16>
 SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem) {
   const int lane = wv::lane();
   const SpmxDev &d = a.dev;
   Q4 *masks = reinterpret_cast<Q4 *>(smem);                         // [18][2] by word length: the key's bytes that are the word's; 0x20 in the others
-  U4 *hot = reinterpret_cast<U4 *>(smem + kWwKeyMaskBytes);
-  uint16_t *disp = reinterpret_cast<uint16_t *>(smem + kWwKeyMaskBytes + kWordHotSlots * 16u);
-  unsigned char *mine_lds = smem + kWwShared + static_cast<uint32_t>(wv::wave_in_block()) * kWwPerWave;
+  U4 *hot = reinterpret_cast<U4 *>(smem + kWwKeyMaskBytes);           // (only where kWwHotIn(MODE): elsewhere the displacements start here)
+  uint16_t *disp = reinterpret_cast<uint16_t *>(smem + kWwShared(MODE) - kUallBuckets * 2u);
+  unsigned char *mine_lds = smem + kWwShared(MODE) + static_cast<uint32_t>(wv::wave_in_block()) * kWwPerWave(MODE);
   uint8_t *ring = mine_lds;
   uint16_t *smask = reinterpret_cast<uint16_t *>(mine_lds + kWwRing + kWwRingPad);
   uint32_t *recq = reinterpret_cast<uint32_t *>(mine_lds + kWwRing + kWwRingPad + kWwMaskBytes);
   U4 *sent = reinterpret_cast<U4 *>(recq + kWwRecs);          // per sentence of the tile: {start, end (positions in the tile's unit stream), arena slot}
   U2 *sent_ua = reinterpret_cast<U2 *>(sent + 64);            // ... the address of its first unit
   uint32_t *s_nids = reinterpret_cast<uint32_t *>(sent_ua + 64), *s_stat = s_nids + 64, *s_first = s_stat + 64;
-  uint32_t *s_n0 = s_first + 64, *s_x0 = s_n0 + 64;            // (second round) ids / bound in front of where the sentence is taken up
+  // (second round only -- the other modes' block ends at s_first) ids / bound in front of where the sentence is taken up
+  uint32_t *s_n0 = MODE == kWmDyn ? s_first + 64 : nullptr, *s_x0 = MODE == kWmDyn ? s_first + 128 : nullptr;
   {   // the shared read-only table (every wave writes the same values: no workgroup barrier)
     if (lane < 18) {
       const uint32_t L = static_cast<uint32_t>(lane);
@@ -161,13 +193,14 @@ SPMX_DEVICE void encode_wordwave_block(const EncodeArgs &a, unsigned char *smem)
     wv::atomic_add(a.arena_head, static_cast<unsigned long long>(a.arena_first));
   WwStage SA{}, SB{};                                               // the two batches of the word pipeline (below)
   uint32_t dyn_warm = 0u;                                           // (collecting round) batches for which stage A still asks the call-local memo's tags
+  // the next tile this wavefront takes by its own index (ww_next_tile): a scalar
+  uint32_t own_tile = wv::uniform(static_cast<uint32_t>(wv::block_id() * wv::waves_per_block() + wv::wave_in_block()));
   for (;;) {
     const unsigned long long cs = wv::clock();
-    uint32_t c = 0, first = 0, ucnt = 0, got = 0;
-    if (lane == 0) got = next_tile(a, &c, &first, &ucnt) ? 1u : 0u;
-    got = wv::shfl(got, 0);
-    if (!got) break;
-    c = wv::shfl(c, 0); first = wv::shfl(first, 0); ucnt = wv::shfl(ucnt, 0);
+    const U4 tl = ww_next_tile<MODE>(a, lane, own_tile);
+    if (!tl.x) break;
+    if (MODE != kWmDyn && own_tile < a.static_tiles) own_tile += a.static_stride;
+    const uint32_t c = tl.y, first = tl.z, ucnt = tl.w;
     const bool direct = a.direct != 0u;
     const uint32_t *list = a.lists ? a.lists + static_cast<uint64_t>(c) * a.n : nullptr;
     const bool have = static_cast<uint32_t>(lane) < ucnt;

@@ -1830,7 +1830,8 @@ class SentencePieceProcessor:
         launch, 3 sentence-per-wave BPE, 4 long / wave-cooperative form, 5 word form first round, 6 second round): dict(kernel, kernel_ms, sentences, raw_bytes, ids, bytes,
         phase_cycles) + total_ms + path (sentences that waited in a wave's backlog / went to the overflow list / took
         the long form / failed; arena_retries: encodes of the batch again with a larger id arena; long_launches: launches of
-        the long form, slot 4)."""
+        the long form, slot 4; word_waves_first / word_waves_second: wavefronts per workgroup the word-per-lane form's first
+        and second round were launched with, 0 where the round did not take that form)."""
         self._need()
         ms = np.zeros(8, dtype=np.float32)
         sent, raw, ids, byt = (np.zeros(8, dtype=np.uint64) for _ in range(4))
@@ -1851,5 +1852,6 @@ class SentencePieceProcessor:
                                                         (int(x) for x in cyc[5 * c:5 * c + 5]))))
                              for c in range(k)],
                     path=dict(backlog=int(path[0]), overflow=int(path[1]), long=int(path[2]), failed=int(path[3]),
-                              arena_retries=int(path[4]), long_launches=int(path[5])),
+                              arena_retries=int(path[4]), long_launches=int(path[5]),
+                              word_waves_first=int(path[6]), word_waves_second=int(path[7])),
                     total_ms=float(tot.value))
