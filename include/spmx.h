@@ -491,6 +491,35 @@ int spmx_sample_encode_and_score_batch_device(spmx_handle *h, const void *d_text
 int spmx_encode_batch_original(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, int32_t **ids,
                                uint64_t **id_offsets);
 
+/* ---- expected piece counts: the unigram trainer's E-step under the loaded model ----------------------------------------
+ * What unigram::Trainer::RunEStep (src/unigram_model_trainer.cc:318-367) computes per training sentence, for a batch:
+ * the lattice of Lattice::SetSentence / Model::PopulateNodes over the normalized sentence, Lattice::PopulateMarginal
+ * (src/unigram_model.cc:235-261: forward, backward, exp(alpha + score + beta - Z) per node -- the reference's float
+ * recurrences in its order) and the node count of Lattice::Viterbi().  Sentence s has the weight freq[s]
+ * (NULL: 1).  Unknown characters are counted under unk_id; byte-fallback pieces never are (the marginal is a lattice
+ * quantity).  Unigram models only: INTERNAL "ExpectedCounts is not available for the current model." otherwise.
+ *
+ * Counts are FIXED POINT with SPMX_EXPECTED_FRAC_BITS fraction bits: a node adds the integer
+ * llrint(freq * p * 2^24) (to nearest, ties to even) to the 64-bit accumulator of its piece, so a result does not depend on
+ * the launch shape, the order of the adds or where a corpus is cut into batches -- batches add up exactly.  Expected count
+ * = acc / 2^24; a node is quantized by at most 2^-25; an accumulator holds 2^40 (about 1.1e12) weighted occurrences of a
+ * piece before it wraps.
+ *   log_z[s]          log Z of sentence s as a float, NOT multiplied by freq[s]; 0 for a sentence that is empty after
+ *                     normalization (which adds nothing and has 0 nodes)
+ *   viterbi_nodes[s]  nodes on the best path (Lattice::Viterbi, all-float), before any id rule: a run of unknown
+ *                     characters counts one per character
+ * No length limit.  n == 0 is valid. */
+#define SPMX_EXPECTED_FRAC_BITS 24
+/* device form: text, offsets, freq (nullable) on the device; d_acc[piece_size] is ADDED to; d_log_z / d_viterbi_nodes
+   [n], nullable; stream-ordered apart from the synchronisations the lattice launches have (n == 0: nothing is touched) */
+int spmx_expected_counts_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets,
+                                      uint64_t n, const uint32_t *d_freq, unsigned long long *d_acc, float *d_log_z,
+                                      uint32_t *d_viterbi_nodes, void *stream);
+/* host form: expected[piece_size] doubles, OVERWRITTEN (= acc / 2^24, exact below 2^29); log_z / viterbi_nodes malloc'ed
+   [n], released with spmx_free(), nullable */
+int spmx_expected_counts_batch(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, const uint32_t *freq,
+                               double *expected, float **log_z, uint32_t **viterbi_nodes);
+
 /* ---- corpus packer ------------------------------------------------------
  * The caller-side step of the reference's spm_encode (src/spm_encode_main.cc:159-165: std::getline over the input
  * file, one Encode per line) on the device: a file image with '\n'-terminated lines -> the packed text (without

@@ -619,6 +619,31 @@ class SentencePieceProcessor {
     spmx_free(e);
     return FromHandle(rc);
   }
+  // ---- expected piece counts: the unigram trainer's E-step under this model (unigram::Trainer::RunEStep,
+  // src/unigram_model_trainer.cc:318-367; no public method of the reference has it).  expected[id] = the sum over the inputs
+  // of freq[s] (empty: all 1) times the marginal probability of every lattice node that carries id, accumulated in fixed
+  // point (spmx.h SPMX_EXPECTED_FRAC_BITS); log_z[s] the sentence's log likelihood, viterbi_nodes[s] the nodes on its
+  // best path ----
+  util::Status ExpectedCounts(const std::vector<std::string_view> &inputs, const std::vector<uint32_t> &freq /* empty: all 1 */,
+                              std::vector<double> *expected, std::vector<float> *log_z = nullptr,
+                              std::vector<uint32_t> *viterbi_nodes = nullptr) const {
+    if (!h_) return status();
+    if (!expected) return util::Status(util::StatusCode::kInternal, "output container is null");
+    if (!freq.empty() && freq.size() != inputs.size()) return util::Status(util::StatusCode::kInternal, "freq must have one entry per input");
+    std::string text;
+    std::vector<uint64_t> offs{0};
+    for (const std::string_view &s : inputs) { text.append(s.data() ? s.data() : "", s.size()); offs.push_back(text.size()); }
+    expected->assign(static_cast<size_t>(spmx_piece_size(h_)), 0.0);
+    float *z = nullptr;
+    uint32_t *v = nullptr;
+    const int rc = spmx_expected_counts_batch(h_, text.data(), offs.data(), inputs.size(), freq.empty() ? nullptr : freq.data(),
+                                              expected->data(), log_z ? &z : nullptr, viterbi_nodes ? &v : nullptr);
+    if (rc == 0 && log_z) log_z->assign(z, z + inputs.size());
+    if (rc == 0 && viterbi_nodes) viterbi_nodes->assign(v, v + inputs.size());
+    spmx_free(z);
+    spmx_free(v);
+    return FromHandle(rc);
+  }
   virtual util::Status SampleEncodeAndScore(std::string_view input, int num_samples, float alpha, bool wor, bool include_best,
                                             std::vector<std::pair<std::vector<int>, float>> *ids) const {
     return SampleEncodeAndScore(input, num_samples, alpha, wor, include_best, NextScoreSeed(), ids);

@@ -131,6 +131,10 @@ SYMBOLS = [
     ("spmx_sample_encode_and_score_batch_device", C.c_int,
      [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_int, C.c_float, C.c_int, C.c_int, _U64, C.c_void_p, _U64, C.c_void_p,
       C.c_void_p, C.c_void_p, _U64, C.c_void_p, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),
+    ("spmx_expected_counts_batch_device", C.c_int,
+     [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("spmx_expected_counts_batch", C.c_int,
+     [_H, C.c_void_p, C.c_void_p, _U64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("spmx_encode_batch_original", C.c_int, [_H, C.c_void_p, C.c_void_p, _U64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("spmx_split_lines_device", C.c_int,
      [_H, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, _U64, C.c_void_p, C.POINTER(_U64), C.POINTER(_U64)]),

@@ -251,6 +251,9 @@ struct Workspace {
   DevBuf<uint32_t> d_lc_len;             // lattice results -> CSR (kernels_latticecsr.h): per result its length and its place in
   DevBuf<unsigned long long> d_lc_src;   // the arena; the two offset arrays where the caller's cannot take them (a capacity query)
   DevBuf<uint64_t> d_lc_ro, d_lc_io;
+  DevBuf<unsigned long long> d_es_acc;   // spmx_expected_counts_batch: the accumulator, the weights and the per-sentence outputs
+  DevBuf<uint32_t> d_es_freq, d_es_nodes;
+  DevBuf<float> d_es_logz;
   const uint8_t *lit_bytes = nullptr;    // set for the duration of one spmx_decode_batch_pieces call
   const uint32_t *lit_offs = nullptr;
   uint32_t n_lit = 0;
@@ -280,6 +283,7 @@ struct Workspace {
     d_res_score.Free(); d_dyn_tag.Free(); d_dyn_ent.Free(); d_dyn_list.Free(); d_resume.Free(); d_text.Free(); d_offs.Free(); d_id_offs.Free(); d_ids.Free(); d_dn_text.Free(); d_dn_offs.Free();
     d_tt_len.Free(); d_tt_rec.Free(); d_tt_start.Free(); d_tt_noffs.Free(); d_tt_out.Free();
     d_lc_len.Free(); d_lc_src.Free(); d_lc_ro.Free(); d_lc_io.Free();
+    d_es_acc.Free(); d_es_freq.Free(); d_es_nodes.Free(); d_es_logz.Free();
     d_lit_bytes.Free(); d_lit_offs.Free(); d_dec_ids.Free(); d_dec_poffs.Free();
     h_text.Free(); h_offs.Free(); h_id_offs.Free();
     if (d_ctrl) (void)hipFree(d_ctrl);
@@ -2681,10 +2685,12 @@ namespace {
 // Leaves the results where the kernel writes them -- d_counts (results per sentence), d_res_off / d_span_begin (lengths) /
 // d_res_score per slot [n][K], the id arena d_arena and, for the spans form, d_arena_tb / d_tok_begin -- complete, the
 // stream synchronized, and *used ids in the arena.  max_raw: the longest sentence in raw bytes (the first launch's
-// capacities follow it).  mode and K as LatticeBatchHost documents them.
+// capacities follow it).  mode and K as LatticeBatchHost documents them; mode 6 (the E-step, spmx_expected_counts_batch) has
+// no result rows: its outputs are `es`.
+struct EStepIo { const uint32_t *freq; unsigned long long *acc; float *log_z; uint32_t *viterbi_nodes; };
 int LatticeLaunch(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
                   uint64_t max_raw, int mode, uint32_t K, float inv_theta, uint64_t seed, uint64_t index_base, int include_best,
-                  bool spans, hipStream_t st, const char *what, uint64_t *used) {
+                  bool spans, hipStream_t st, const char *what, uint64_t *used, const EStepIo *es = nullptr) {
   uint64_t ntotal = 0;
   int rc = GrowOnce(h, ws->d_norm, 2 * text_bytes + 4 * n + 64, &ntotal, 0, [&] {
     return NormalizeDevice(h, ws, d_text, d_offsets, n, ws->d_norm.p, ws->d_norm.cap, ws->d_id_offs.p, nullptr, st, &ntotal, true);
@@ -2694,6 +2700,7 @@ int LatticeLaunch(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t
   NBestArgs a{};
   a.dev = h->dev; a.norm = ws->d_norm.p; a.norm_offs = ws->d_id_offs.p; a.n = static_cast<uint32_t>(n); a.nbest = K;
   a.mode = static_cast<uint32_t>(mode); a.inv_theta = inv_theta; a.seed = seed; a.index_base = index_base; a.include_best = include_best ? 1u : 0u;
+  if (es) { a.freq = es->freq; a.acc = es->acc; a.log_z = es->log_z; a.viterbi_nodes = es->viterbi_nodes; }
   const uint64_t hyps0 = static_cast<uint64_t>(K) * 512;   // (a C2 sentence's n-best 5 makes ~1,000; what outgrows the slice runs again)
   // The first launch's capacities follow the batch: a slice sized for 1024 bytes and 16384 nodes is 0.7 MB a lane, of
   // which a 126-byte sentence touches a twentieth, and the lanes in flight are what the budget holds (200 k sentences,
@@ -2704,8 +2711,8 @@ int LatticeLaunch(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t
   uint64_t nodes0 = (len0 + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
   if (nodes0 > kNbMaxNodes) nodes0 = kNbMaxNodes;
   const uint64_t hyps_min = h->nbest_hyps_min;
-  // (modes 1 and 4 keep alpha there, len0 + 1 floats of the 2048; mode 3 alpha and H, 2050 floats at 1024 bytes)
-  const uint32_t max_hyps0 = mode == 3 ? static_cast<uint32_t>(len0 / 2 + 2) : (mode != 0 && mode != 5) ? 512u : static_cast<uint32_t>(hyps0 < hyps_min ? hyps_min : (hyps0 > 262144 ? 262144 : hyps0));
+  // (modes 1 and 4 keep alpha there, len0 + 1 floats of the 2048; mode 3 alpha and H, mode 6 alpha and beta, 2050 floats at 1024 bytes)
+  const uint32_t max_hyps0 = (mode == 3 || mode == 6) ? static_cast<uint32_t>(len0 / 2 + 2) : (mode != 0 && mode != 5) ? 512u : static_cast<uint32_t>(hyps0 < hyps_min ? hyps_min : (hyps0 > 262144 ? 262144 : hyps0));
   const uint64_t budget = h->nbest_budget;                  // HBM for the lanes' slices
   HIP_OR_RETURN(h, ws->d_res_off.Reserve(n * K + 1));
   HIP_OR_RETURN(h, ws->d_span_begin.Reserve(n * K + 1));     // result lengths
@@ -2714,7 +2721,7 @@ int LatticeLaunch(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t
   HIP_OR_RETURN(h, ws->d_lists.Reserve(2 * n + 2));          // the sentences beyond a launch's capacities (two lists, in turn)
   a.res_off = ws->d_res_off.p; a.res_len = ws->d_span_begin.p; a.res_score = ws->d_res_score.p; a.res_count = ws->d_counts.p;
   a.status = &ws->d_ctrl->status; a.arena_head = &ws->d_ctrl->arena_head;
-  uint64_t arena_need = (ntotal + (4 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * n) * (K < 8 ? K : 8) + 1024;
+  uint64_t arena_need = mode == 6 ? 64 : ((ntotal + (4 + static_cast<uint64_t>(h->dev.n_prefix + h->dev.n_suffix)) * n) * (K < 8 ? K : 8) + 1024);
   for (int attempt = 0; attempt < 12; ++attempt) {
     HIP_OR_RETURN(h, ws->d_arena.Reserve(arena_need));
     a.arena = ws->d_arena.p; a.arena_cap = ws->d_arena.cap;
@@ -2747,7 +2754,7 @@ int LatticeLaunch(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t
       // and one UNK node.
       const uint64_t L = ws->h_ctrl->side.over_max_raw > kNbMaxLen ? ws->h_ctrl->side.over_max_raw : kNbMaxLen;
       const uint64_t nodes = (L + 2) * (static_cast<uint64_t>(h->tables.max_prefixes) + 1) + 2;
-      uint64_t hy = mode == 3 ? L / 2 + 512 : (mode != 0 && mode != 5) ? L / 4 + 512 : (static_cast<uint64_t>(K) * (L + 2) * 4 + 16384) * hy_scale;   // modes 1, 4: alpha[L + 1] floats; mode 3: H[L + 1] too
+      uint64_t hy = (mode == 3 || mode == 6) ? L / 2 + 512 : (mode != 0 && mode != 5) ? L / 4 + 512 : (static_cast<uint64_t>(K) * (L + 2) * 4 + 16384) * hy_scale;   // modes 1, 4: alpha[L + 1] floats; mode 3: H[L + 1] too; mode 6: beta[L + 1] too
       if (hy < max_hyps0 * hy_scale) hy = max_hyps0 * hy_scale;
       if (L >= (1ull << 31) || nodes >= (1ull << 32) || hy >= (1ull << 32)) return Fail(h, kOutOfRange, "a sentence is too long for the lattice");
       a.max_len = static_cast<uint32_t>(L); a.max_nodes = static_cast<uint32_t>(nodes); a.max_hyps = static_cast<uint32_t>(hy);
@@ -2778,6 +2785,8 @@ int LatticeLaunch(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t
     }
     const uint32_t stw = ws->h_ctrl->status;
     if (stw & kStNbestOverflow) return Fail(h, kResourceExhausted, std::string(what) + ": the agenda of a sentence exceeds the device capacities");
+    // (mode 6 takes nothing from the arena and ADDS to its output: a second pass over the batch would count it twice)
+    if (mode == 6 && (stw & kStArenaOverflow)) return Fail(h, kInternal, std::string(what) + ": the id arena is not used");
     // (a lane stops at its first result that does not fit, so arena_head is a lower bound: grow geometrically)
     if (stw & kStArenaOverflow) { arena_need = 4 * ws->d_arena.cap > ws->h_ctrl->arena_head + 1024 ? 4 * ws->d_arena.cap : ws->h_ctrl->arena_head + 1024; continue; }
     *used = ws->h_ctrl->arena_head;
@@ -3339,6 +3348,94 @@ int LatticeBatchDevice(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uin
   return kOk;
 }
 }  // namespace
+
+/* ---- expected piece counts: the unigram trainer's E-step under the loaded model (kernels_nbest.h mode 6) -------------- */
+namespace {
+constexpr const char *kExpectedCountsRefusal = "ExpectedCounts is not available for the current model.";
+
+// On a leased workspace: the longest sentence (one word to the host, as LatticeBatchDevice has it), then the lattice launches.
+int ExpectedCountsWs(spmx_handle *h, Workspace *ws, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_offsets, uint64_t n,
+                     const EStepIo &io, hipStream_t stream) {
+  if (n >= (1ull << 32) - 64) return Fail(h, kInvalidArgument, "more than 2^32 - 64 sentences in one batch");
+  const uint64_t wide = static_cast<uint64_t>(h->n_cu) * 16;
+  const uint64_t units = (n + 63) / 64;
+  unsigned long long max_raw = 0;
+  unsigned long long *d_max = &ws->d_ctrl->lattice_max_raw;
+  HIP_OR_RETURN(h, hipMemsetAsync(d_max, 0, sizeof(*d_max), stream));
+  LatticeMaxLenArgs ma{d_offsets, n, d_max};
+  HIP_OR_RETURN(h, LaunchLatticeMaxLen(ma, static_cast<int>(units < 1 ? 1 : (units < wide ? units : wide)), stream));
+  HIP_OR_RETURN(h, hipMemcpyAsync(&max_raw, d_max, sizeof(max_raw), hipMemcpyDeviceToHost, stream));
+  HIP_OR_RETURN(h, hipStreamSynchronize(stream));
+  HIP_OR_RETURN(h, ws->d_id_offs.Reserve(n + 1));
+  uint64_t used = 0;
+  return LatticeLaunch(h, ws, d_text, text_bytes, d_offsets, n, max_raw, 6, 1, 1.f, 0, 0, 0, false, stream, "ExpectedCounts", &used, &io);
+}
+}  // namespace
+
+int spmx_expected_counts_batch_device(spmx_handle *h, const void *d_text, uint64_t text_bytes, const uint64_t *d_offsets,
+                                      uint64_t n, const uint32_t *d_freq, unsigned long long *d_acc, float *d_log_z,
+                                      uint32_t *d_viterbi_nodes, void *stream) {
+  if (!h) return kInvalidArgument;
+  return Guard(h, [&]() -> int {
+    if (h->model.model_type != kUnigram) return Fail(h, kInternal, kExpectedCountsRefusal);
+    if (n == 0) return kOk;                                 // d_acc stays as it is
+    if (!d_offsets) return Fail(h, kInvalidArgument, "null offsets");
+    if (!d_acc) return Fail(h, kInternal, "output container is null");
+    HIP_OR_RETURN(h, hipSetDevice(h->device));
+    Lease L(h);
+    if (int rc = L.Ready(); rc != kOk) return rc;
+    const EStepIo io{d_freq, d_acc, d_log_z, d_viterbi_nodes};
+    return ExpectedCountsWs(h, L.ws.get(), static_cast<const uint8_t *>(d_text), text_bytes, d_offsets, n, io, static_cast<hipStream_t>(stream));
+  });
+}
+
+int spmx_expected_counts_batch(spmx_handle *h, const char *text, const uint64_t *offsets, uint64_t n, const uint32_t *freq,
+                               double *expected, float **log_z, uint32_t **viterbi_nodes) {
+  if (!h) return kInvalidArgument;
+  if (!expected) return Fail(h, kInternal, "output container is null");
+  return Guard(h, [&]() -> int {
+    if (log_z) *log_z = nullptr;
+    if (viterbi_nodes) *viterbi_nodes = nullptr;
+    if (h->model.model_type != kUnigram) return Fail(h, kInternal, kExpectedCountsRefusal);
+    const uint64_t V = h->model.pieces.size();
+    for (uint64_t i = 0; i < V; ++i) expected[i] = 0.0;
+    float *hz = log_z ? static_cast<float *>(calloc(n ? n : 1, sizeof(float))) : nullptr;
+    uint32_t *hv = viterbi_nodes ? static_cast<uint32_t *>(calloc(n ? n : 1, sizeof(uint32_t))) : nullptr;
+    struct Hold { float *z; uint32_t *v; ~Hold() { free(z); free(v); } } hold{hz, hv};
+    if ((log_z && !hz) || (viterbi_nodes && !hv)) return Fail(h, kResourceExhausted, "out of host memory");
+    if (n) {
+      if (!offsets) return Fail(h, kInvalidArgument, "null offsets");
+      HIP_OR_RETURN(h, hipSetDevice(h->device));
+      Lease L(h);
+      if (int rc = L.Ready(); rc != kOk) return rc;
+      Workspace *ws = L.ws.get();
+      hipStream_t st = ws->stream;
+      const uint64_t base = offsets[0], text_bytes = offsets[n] - base;
+      HIP_OR_RETURN(h, ws->d_text.Reserve(text_bytes + 32));
+      HIP_OR_RETURN(h, ws->d_offs.Reserve(n + 1));
+      HIP_OR_RETURN(h, ws->d_es_acc.Reserve(V + 1));
+      HIP_OR_RETURN(h, ws->d_es_nodes.Reserve(n));
+      HIP_OR_RETURN(h, ws->d_es_logz.Reserve(n));
+      if (freq) HIP_OR_RETURN(h, ws->d_es_freq.Reserve(n));
+      if (text_bytes) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_text.p, text + base, text_bytes, hipMemcpyHostToDevice, st));
+      HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_offs.p, offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      if (freq) HIP_OR_RETURN(h, hipMemcpyAsync(ws->d_es_freq.p, freq, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      HIP_OR_RETURN(h, hipMemsetAsync(ws->d_es_acc.p, 0, V * sizeof(unsigned long long), st));
+      const EStepIo io{freq ? ws->d_es_freq.p : nullptr, ws->d_es_acc.p, ws->d_es_logz.p, ws->d_es_nodes.p};
+      if (int rc = ExpectedCountsWs(h, ws, ws->d_text.p - base, text_bytes, ws->d_offs.p, n, io, st); rc != kOk) return rc;
+      std::vector<unsigned long long> acc(V);
+      HIP_OR_RETURN(h, hipMemcpyAsync(acc.data(), ws->d_es_acc.p, V * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      if (hz) HIP_OR_RETURN(h, hipMemcpyAsync(hz, ws->d_es_logz.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+      if (hv) HIP_OR_RETURN(h, hipMemcpyAsync(hv, ws->d_es_nodes.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIP_OR_RETURN(h, hipStreamSynchronize(st));
+      // (exact while the accumulator is below 2^53 -- a count below 2^29; beyond that the nearest double)
+      for (uint64_t i = 0; i < V; ++i) expected[i] = static_cast<double>(acc[i]) * (1.0 / static_cast<double>(1ll << kNbExpectedFracBits));
+    }
+    if (log_z) { *log_z = hz; hold.z = nullptr; }
+    if (viterbi_nodes) { *viterbi_nodes = hv; hold.v = nullptr; }
+    return kOk;
+  });
+}
 
 namespace {
 // NBestEncode into the caller's device buffers, on a leased workspace; nbest_size within [1, 1024], a unigram model

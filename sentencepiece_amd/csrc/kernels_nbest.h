@@ -21,6 +21,7 @@ constexpr uint32_t kNbMaxLen = 1024;        // normalized (device) bytes per sen
 constexpr uint32_t kNbMaxNodes = 16384;     // lattice nodes per sentence, first launch
 constexpr uint32_t kNbAgendaCap = 10000 + 512;   // :487 kMaxAgendaSize + the largest fan-in handled
 constexpr uint32_t kStNbestOverflow = 1u << 5;   // status: a per-sentence capacity was exceeded
+constexpr int kNbExpectedFracBits = 24;          // mode 6: a node adds llrint(freq * p * 2^24) to its piece (SPMX_EXPECTED_FRAC_BITS)
 
 template <typename IX>
 struct NbNodeT { IX pos, length, byte_begin, byte_len; int32_t id; float score, backtrace; uint32_t prev; };   // 24 / 32 bytes
@@ -34,7 +35,7 @@ SPMX_HD inline uint64_t NbestLaneBytes(uint64_t max_len, uint64_t max_nodes, uin
        + NbAlign16((max_len + 3) * 4ull)                     // end_off: CSR offsets of the nodes ending at a position
        + NbAlign16(max_nodes * ix)                           // end_idx
        + NbAlign16((max_len + 2) * ix)                       // cursor per position
-       + NbAlign16(max_hyps * sizeof(NbHyp))                 // hypotheses (modes 1 and 4: alpha, one float per position; mode 3: alpha and H)
+       + NbAlign16(max_hyps * sizeof(NbHyp))                 // hypotheses (modes 1 and 4: alpha, one float per position; mode 3: alpha and H; mode 6: alpha and beta)
        + kNbAgendaCap * 4ull + 64;
 }
 
@@ -49,7 +50,9 @@ struct NBestArgs {
                                 // (:161-198), the kOriginal encoder (:674-692); 3 Lattice::CalculateEntropy(inv_theta)
                                 // (:263-291): one result without ids, its score the entropy; 4 SampleEncodeAndScore with
                                 // replacement (:828-843): `nbest` draws of mode 1's sampler, each with its log probability;
-                                // 5 SampleEncodeAndScore without replacement (:771-827): mode 0's A* with Gumbel keys
+                                // 5 SampleEncodeAndScore without replacement (:771-827): mode 0's A* with Gumbel keys;
+                                // 6 the unigram trainer's E-step of one sentence (Lattice::PopulateMarginal :235-261 and
+                                // the node count of Lattice::Viterbi): no result rows, the outputs below
   uint32_t include_best;        // mode 5: the Viterbi path first, with score 0, and out of the samples
   float inv_theta;              // modes 1, 3, 4, 5
   uint64_t seed;                // mode 1: the lanes' generators are keyed by (seed, sentence index); mode 4: draw j of
@@ -78,6 +81,11 @@ struct NBestArgs {
   float *res_score;             // [n][nbest]
   uint32_t *res_count;          // [n]
   uint32_t *status;
+  // mode 6
+  const uint32_t *freq;         // [n] the sentences' weights (null: all 1)
+  unsigned long long *acc;      // [piece_size] expected counts in fixed point, kNbExpectedFracBits fraction bits: ADDED to
+  float *log_z;                 // [n] log Z of the sentence, not weighted (null: not asked for)
+  uint32_t *viterbi_nodes;      // [n] nodes on the best path (null: not asked for)
 };
 
 // std::push_heap with comp(a, b) = a->fx < b->fx
@@ -176,6 +184,11 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     return;
   }
   if (size == 0 && (a.mode == 4u || a.mode == 5u)) return;         // :745-747 no result (the caller's "returns empty result.")
+  if (size == 0 && a.mode == 6u) {               // no node: Z = 0, nothing expected, an empty best path
+    if (a.log_z) a.log_z[s] = 0.f;
+    if (a.viterbi_nodes) a.viterbi_nodes[s] = 0u;
+    return;
+  }
   if (size == 0) {                               // unigram_model.cc:688-690: one empty result, score 0
     int32_t *dst = alloc(n_extra);
     if (dst) put_extras(dst, 0);
@@ -269,7 +282,7 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     }
     return best;
   };
-  if (a.mode == 0u || a.mode == 2u || (a.mode == 5u && a.include_best)) {
+  if (a.mode == 0u || a.mode == 2u || a.mode == 6u || (a.mode == 5u && a.include_best)) {
     for (uint32_t i = 2; i < n_nodes; ++i) nodes[i].backtrace = best_into(nodes[i].pos, nodes[i].score, &nodes[i].prev);
     nodes[1].backtrace = best_into(len, 0.f, &nodes[1].prev);
   }
@@ -410,6 +423,59 @@ SPMX_DEVICE void nbest_lane(const NBestArgs &a, uint32_t s, uint8_t *mine) {
     st = a.seed * 0x9E3779B97F4A7C15ull + (a.index_base + static_cast<unsigned long long>(s) + 1ull) * 0xD1B54A32D192ED03ull;
     const uint32_t first = draw_path(alpha);
     emit_path([&] { return first; }, [&](uint32_t h) { return nodes[h].prev; }, [&](uint32_t h) { return h == 1u; }, 0.f);
+    return;
+  }
+  if (a.mode == 6u) {
+    // ---- The E-step of one sentence (unigram::Trainer::RunEStep, src/unigram_model_trainer.cc:318-367):
+    // Lattice::PopulateMarginal(freq, &expected) (:235-261) and the size of Lattice::Viterbi()'s path.  alpha of a node
+    // depends on its begin position, beta (BackwardAlgorithm :218-233) on its end position: A and B, one float per
+    // position.  The reference's number is the contract, as in modes 3 and 4: its order, float, nothing contracted.
+    // Every capacity is checked BEFORE the first add to `acc`: a sentence that is set aside has added nothing, the wide
+    // launch counts it once. ----
+#pragma clang fp contract(off)
+    float *A = reinterpret_cast<float *>(hy);
+    float *B = A + (len + 1);
+    const uint64_t room = static_cast<uint64_t>(a.max_hyps) * (sizeof(NbHyp) / sizeof(float));
+    if (2ull * (static_cast<uint64_t>(len) + 1ull) > room) { set_aside(); return; }
+    A[0] = 0.f;                                         // ForwardAlgorithm(1.0) (:200-216)
+    for (int pos = 1; pos <= len; ++pos) {
+      float acc = 0.f;
+      for (uint32_t l = end_off[pos]; l < end_off[pos + 1]; ++l) {
+        const NbNode &ln = nodes[end_idx[l]];
+        acc = lse(acc, ln.score + A[ln.pos], l == end_off[pos]);
+      }
+      A[pos] = acc;
+    }
+    // BackwardAlgorithm: the nodes beginning at a position are a run of `nodes` (sorted by position, in insertion order
+    // -- the trie's matches by increasing length, the unknown node last); positions from the right
+    B[len] = 0.f;
+    for (uint32_t hi = n_nodes; hi > 2u;) {
+      uint32_t lo = hi - 1u;
+      const int pos = nodes[lo].pos;
+      while (lo > 2u && static_cast<int>(nodes[lo - 1u].pos) == pos) --lo;
+      float acc = 0.f;
+      for (uint32_t i = lo; i < hi; ++i) acc = lse(acc, nodes[i].score + B[static_cast<int>(nodes[i].pos) + static_cast<int>(nodes[i].length)], i == lo);
+      B[pos] = acc;
+      hi = lo;
+    }
+    const float Z = A[len];
+    const double weight = static_cast<double>(a.freq ? a.freq[s] : 1u);
+    for (uint32_t i = 2; i < n_nodes; ++i) {
+      const NbNode &x = nodes[i];
+      if (x.id < 0) continue;                           // :250
+      const float u = A[x.pos] + x.score;
+      const float v = u + B[static_cast<int>(x.pos) + static_cast<int>(x.length)];
+      const float t = v - Z;
+      const double p = exp(static_cast<double>(t));
+      const long long q = llrint(weight * p * static_cast<double>(1ll << kNbExpectedFracBits));   // to nearest, ties to even
+      if (q > 0) wv::atomic_add(a.acc + x.id, static_cast<unsigned long long>(q));
+    }
+    if (a.log_z) a.log_z[s] = Z;
+    if (a.viterbi_nodes) {                              // lattice.Viterbi().first.size(): nodes, before any id rule
+      uint32_t cnt = 0;
+      for (uint32_t cur = nodes[1].prev; cur != 0u; cur = nodes[cur].prev) ++cnt;
+      a.viterbi_nodes[s] = cnt;
+    }
     return;
   }
   if (a.mode == 3u || a.mode == 4u) {

@@ -1746,6 +1746,77 @@ class SentencePieceProcessor:
                                                output_format.encode(), C.byref(ns), C.byref(ni)))
         return int(ns.value), int(ni.value)
 
+    # ------------------------------------------- expected piece counts ----
+    def ExpectedCountsPacked(self, text, offsets, freq=None):
+        """Packed host arrays -> ``(expected float64[GetPieceSize()], log_z float32[n], viterbi_nodes uint32[n])``: the
+        unigram trainer's E-step under this model (unigram models only).  ``expected[id]`` is the sum over the sentences of
+        ``freq[s]`` (uint32, default 1) times the marginal probability of every lattice node that carries ``id`` -- the
+        reference's float forward-backward in its order, accumulated in fixed point with 24 fraction bits,
+        so batches add up exactly.  Unknown characters count under ``unk_id()``.  ``log_z[s]`` is the sentence's log
+        likelihood (not weighted), ``viterbi_nodes[s]`` the nodes on its best path."""
+        self._need()
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        if freq is not None:
+            freq = np.ascontiguousarray(freq, dtype=np.uint32)
+            if len(freq) != n:
+                raise ValueError("freq must have one entry per sentence")
+        expected = np.zeros(self.GetPieceSize(), dtype=np.float64)
+        pz, pv = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.spmx_expected_counts_batch(self._h, text.ctypes.data if len(text) else None, offs.ctypes.data, n,
+                                                         freq.ctypes.data if freq is not None and n else None,
+                                                         expected.ctypes.data, C.byref(pz), C.byref(pv)))
+        try:
+            log_z = (np.ctypeslib.as_array(C.cast(pz, C.POINTER(C.c_float)), shape=(n,)).copy() if n else np.zeros(0, dtype=np.float32))
+            nodes = (np.ctypeslib.as_array(C.cast(pv, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint32))
+        finally:
+            self._lib.spmx_free(pz)
+            self._lib.spmx_free(pv)
+        return expected, log_z, nodes
+
+    def ExpectedCounts(self, input, freq=None):
+        """``ExpectedCountsPacked`` of a str or a list of str / bytes: the same three arrays."""
+        single, raw, text, offs = self._pack_items(input)
+        return self.ExpectedCountsPacked(text, offs, freq)
+
+    def ExpectedCountsDevice(self, d_text, d_offsets, d_freq=None, d_acc=None, stream=None):
+        """``ExpectedCountsPacked`` over torch tensors on this processor's GPU: ``d_text`` uint8[bytes], ``d_offsets``
+        int64[n + 1], ``d_freq`` int32[n] holding the uint32 weights (None: all 1) -> ``(d_acc, d_log_z float32[n],
+        d_viterbi_nodes int32[n])``.  ``d_acc`` is an int64 tensor ``[GetPieceSize()]`` holding the uint64 bits of the
+        fixed-point accumulators (expected count = acc / 2**24): allocated and zeroed when not given, else ADDED to, so a
+        corpus streams through in batches and the sum does not depend on where it is cut."""
+        import torch
+        self._need()
+        n = d_offsets.numel() - 1
+        dev = d_text.device
+        if d_acc is None:
+            d_acc = torch.zeros(self.GetPieceSize(), dtype=torch.int64, device=dev)
+        elif d_acc.dtype != torch.int64 or not d_acc.is_contiguous() or d_acc.numel() != self.GetPieceSize():
+            raise ValueError("d_acc must be a contiguous int64 tensor of GetPieceSize() entries")
+        if d_freq is not None and (d_freq.dtype != torch.int32 or not d_freq.is_contiguous() or d_freq.numel() != n):
+            raise ValueError("d_freq must be a contiguous int32 tensor with one entry per sentence")
+        if d_offsets.dtype != torch.int64 or not d_offsets.is_contiguous():
+            raise ValueError("d_offsets must be a contiguous int64 tensor")
+        d_log_z = torch.zeros(max(n, 0), dtype=torch.float32, device=dev)
+        d_nodes = torch.zeros(max(n, 0), dtype=torch.int32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream if d_text.is_cuda else 0
+        self._check(self._lib.spmx_expected_counts_batch_device(
+            self._h, d_text.data_ptr() if d_text.numel() else None, d_text.numel(), d_offsets.data_ptr(), n,
+            d_freq.data_ptr() if d_freq is not None and n else None, d_acc.data_ptr(), d_log_z.data_ptr() if n else None,
+            d_nodes.data_ptr() if n else None, stream))
+        return d_acc, d_log_z, d_nodes
+
+    @staticmethod
+    def EStepObjective(log_z, freq=None):
+        """``-sum(freq * log_z) / sum(freq)`` in float64: the objective unigram::Trainer::RunEStep reports
+        (src/unigram_model_trainer.cc:358-364) from the ``log_z`` of ``ExpectedCounts``."""
+        z = np.asarray(log_z, dtype=np.float64)
+        f = np.ones(len(z), dtype=np.float64) if freq is None else np.asarray(freq, dtype=np.float64)
+        total = float(f.sum())
+        return -float(np.dot(f, z)) / total if total else 0.0
+
     # ------------------------------------------- piece frequency counts ----
     def LoadVocabulary(self, filename, threshold):
         """``LoadVocabulary`` (src/sentencepiece_processor.cc:341-362): lines ``token TAB freq``; the tokens whose
